@@ -10,7 +10,11 @@ features already resident in HBM.  Workload at every N: BASELINE.json configs[1]
 SURVEY.md §8(d)); pairs are independent, so ranks shard the batch with NO data-path
 collective (weak scaling).  Rank 0 prints ONE JSON line on stdout.
 
-Extra objects in that line:
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs DIR: the disparity of the last timed step,
+DIR/disparity.npy, float32; with --train the loss and the model state after the last step) and prints the line.  Everything else
+runs only with --full, after the timed region; without it the objects below are null.
+
+Extra objects in that line (--full):
   roofline      the dominant kernel of the step (largest share of the per-kernel HIP-event time; today the split-operand (RAGMI_F32X3)
                 convolution of the level-3 cells, conv3d_x3.hip).  `achieved` = its ALGORITHMIC bytes (input once +
                 output once) or flops per launch / its mean launch duration, priced against the LARGER
@@ -55,6 +59,24 @@ PEAK_HBM_GBS = 8000.0
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 * 10**6      # --dump-outputs: all arrays together stay below this
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as <path>/<name>.npy in float32.  An array larger than its share of
+    DUMP_BYTES is replaced by a fixed sample of its elements (seeded, sorted flat indices: the same ones from run to run), so that
+    two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BYTES // len(arrays) - 4096) // 4          # elements per array (npy header slack)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"bench: outputs written to {path}: {', '.join(sorted(arrays))}")
 
 
 def build_net(device, seed=0, genotype=None):
@@ -492,10 +514,12 @@ def train_cpu_baseline(seed=0):
                       "also runs the Feature Net, the all-reduce, clip and SGD"}
 
 
-def train_leg(device, dist, rank, n_gpus, B, steps, warmup, use_graph, precision, with_cpu=False):
+def train_leg(device, dist, rank, n_gpus, B, steps, warmup, use_graph, precision, with_cpu=False, full=False, dump_dir=None):
     """BASELINE configs[4]: one data-parallel training step per `step` — images -> Feature Net -> cost volume ->
     Matching Net -> Disp -> masked smooth-L1 -> backward -> flat-bucket gradient all-reduce (RCCL) -> clip -> SGD,
     forward and backward on the HIP kernels (rag_amd.autograd).  All units trainable (task 0 of the growth loop).
+    `full`: after the timed region, the phase split, the roofline of the dominant kernel and (with_cpu) the CPU baseline.
+    `dump_dir`: rank 0 writes the last timed step's loss and the model state after it there (dump_outputs).
     Returns the JSON line (rank 0) or None."""
     import rag_amd
     from rag_amd.train import GradBucket, GraphedTrainStep, exchange_and_update, forward_backward, make_optimizer, train_step
@@ -527,22 +551,26 @@ def train_leg(device, dist, rank, n_gpus, B, steps, warmup, use_graph, precision
     dt = timed_region(step, steps, warmup, dist, torch.cuda.synchronize, device)
     if rank != 0:
         return None
-    # rank 0, untimed extra step, eager: phase split + per-call HIP events of the convolution families (roofline of the dominant one)
-    prof = TrainProfiler(rag_amd.ops)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    prof.enabled = True
-    ev[0].record()
-    forward_backward(net, bucket, left, right, gt, precision=precision)
-    ev[1].record()
-    prof.enabled = False
-    exchange_and_update(opt, bucket, clip=5.0, dist=dist)
-    ev[2].record()
-    torch.cuda.synchronize()
-    prof.restore()
-    phases = {"forward_backward_ms_eager": round(ev[0].elapsed_time(ev[1]), 3), "allreduce_clip_sgd_ms": round(ev[1].elapsed_time(ev[2]), 3)}
-    roofline = None
-    dom = prof.dominant()
+    if dump_dir:
+        state = [v.reshape(-1) for v in net.state_dict().values() if v.is_floating_point()]
+        dump_outputs(dump_dir, {"loss": torch.as_tensor(losses[-1]).reshape(1), "model_state": torch.cat(state)})
     ms = dt / steps * 1e3
+    phases, roofline, dom = None, None, None
+    if full:
+        # rank 0, untimed extra step, eager: phase split + per-call HIP events of the convolution families (roofline of the dominant one)
+        prof = TrainProfiler(rag_amd.ops)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        prof.enabled = True
+        ev[0].record()
+        forward_backward(net, bucket, left, right, gt, precision=precision)
+        ev[1].record()
+        prof.enabled = False
+        exchange_and_update(opt, bucket, clip=5.0, dist=dist)
+        ev[2].record()
+        torch.cuda.synchronize()
+        prof.restore()
+        phases = {"forward_backward_ms_eager": round(ev[0].elapsed_time(ev[1]), 3), "allreduce_clip_sgd_ms": round(ev[1].elapsed_time(ev[2]), 3)}
+        dom = prof.dominant()
     if dom is not None:
         (kind, Cin, Cout, Bk, D, Hh, Ww), secs, nlaunch, conv_secs = dom
         vox = float(Bk) * D * Hh * Ww
@@ -563,7 +591,7 @@ def train_leg(device, dist, rank, n_gpus, B, steps, warmup, use_graph, precision
         else:
             roofline = {"bound": "mfma", "achieved": round(flops / per * 1e-12, 2), "peak": peak, "unit": "TFLOP/s",
                         "frac": round(flops / per * 1e-12 / peak, 4), **common}
-    cpu = train_cpu_baseline() if (with_cpu and n_gpus == 1) else None
+    cpu = train_cpu_baseline() if (full and with_cpu and n_gpus == 1) else None
     return {
         "metric": "training stereo pairs/sec at 192x384 D=192 (fwd+bwd+grad all-reduce+SGD step)",
         "value": round(n_gpus * B * steps / dt, 3), "unit": "stereo pairs/s",
@@ -677,7 +705,7 @@ def other_configs(net, lf, rf, out_f32, ref, device, use_graph, dist):
     leg("all_skip", _all_skip)
     # configs[4]: the training step (B=4 at 192x384), its dominant kernel's roofline and the oracle's fwd+bwd beside it
     def _config4_train():
-        line = train_leg(device, dist, 0, 1, TRAIN_B, 5, 2, use_graph, "fp32", with_cpu=ref is not None)
+        line = train_leg(device, dist, 0, 1, TRAIN_B, 5, 2, use_graph, "fp32", with_cpu=ref is not None, full=True)
         res["config4_train"] = {k: line[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "phases_rank0", "loss_first_last",
                                                      "roofline", "cpu_baseline")}
         res["config4_train"]["workload"] = line["config"]["workload"]
@@ -687,6 +715,118 @@ def other_configs(net, lf, rf, out_f32, ref, device, use_graph, dist):
 
     leg("config4_train", _config4_train)
     return res
+
+
+def full_riders(args, net, step, lf, rf, out, dt, graph, prof, device, dist, n_gpus, B):
+    """--full, rank 0, after the timed region: the roofline of the dominant kernel, the CPU baseline with the EPE of the timed path
+    against it, the strict-fp32 leg, the bf16-vs-fp32 EPE, the end-to-end leg and the other BASELINE configurations.
+    Returns the objects of the JSON line under those names."""
+    import rag_amd
+    if graph is not None:   # per-kernel events need eager launches: same kernels, extra pass
+        prof.enabled = True
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        prof.enabled = False
+
+    torch.cuda.synchronize()
+    by = prof.summary()
+    roofline = roofline_of(by, args, dt, graph is not None)
+    if graph is not None and roofline and roofline["kernel"].startswith("conv3d_x3") and "<2," in roofline["kernel"]:
+        # the dominant kernel = the level-3 dual launches: their times INSIDE a replayed graph (dual_launches_in_graph_us) replace the
+        # eager-pass figure in `achieved` / `frac`; the eager one stays beside it
+        try:
+            with torch.no_grad():
+                us = dual_launches_in_graph_us(step, (MAXDISP // 3, H // 3, W // 3))
+        except Exception as exc:      # noqa: BLE001 (a measurement aid: never fatal)
+            log(f"bench: in-graph launch timing failed ({type(exc).__name__}: {exc})")
+            us = []
+        if us and len(us) == roofline["launches_per_step"]:
+            avg = sum(us) / len(us)
+            roofline["avg_launch_us_eager"] = roofline["avg_launch_us"]
+            roofline["avg_launch_us"] = round(avg, 2)
+            roofline["launch_us_in_graph"] = [round(u, 1) for u in us]
+            roofline["avg_launch_us_source"] = ("HIP events on the launch stream around back-to-back replays of a captured hipGraph holding 20 launches "
+                                                "of each of this forward's level-3 dual launches with their own buffers (per-kernel events cannot be "
+                                                "recorded inside a graph on this runtime; events around eager launches — avg_launch_us_eager — read "
+                                                "10-20 % long); rocprofv3's averages of the replayed graph agree: profiles/r05*_step_timeline.txt")
+            if roofline["bound"] == "hbm":
+                gbs = roofline["algorithmic_bytes_per_launch"] / (avg * 1e-6) * 1e-9
+                roofline["achieved"], roofline["frac"] = round(gbs, 1), round(gbs / PEAK_HBM_GBS, 4)
+                tf = roofline["flops_per_launch"] / (avg * 1e-6) * 1e-12
+                roofline["mfma"]["achieved_tflops"], roofline["mfma"]["frac"] = round(tf, 2), round(tf / roofline["mfma"]["peak"], 4)
+            roofline["share_of_step"] = round(sum(us) * 1e-6 / (dt / args.steps), 3)
+    if by:
+        for k, (s_, f_, b_, n_) in sorted(by.items(), key=lambda kv: -kv[1][0]):
+            log(f"  conv3d {'x3 (split operands) channel groups' if k[1] == 'x3' else 'k3 G'}={k[0]} tx={k[1]} R={k[2]} nset={k[3]}: {n_ // args.steps} launches/step, {s_ / args.steps * 1e3:.3f} ms/step, "
+                f"{f_ / s_ * 1e-12:.1f} TFLOP/s, {b_ / s_ * 1e-9:.0f} GB/s (in+out)")
+    cpu = None
+    if n_gpus == 1 and not args.no_cpu_baseline:
+        cpu, ref = cpu_baseline(net, lf.float(), rf.float())
+        from oracle import matching_oracle as O
+        epe = O.epe(out[:1].float().cpu(), ref)
+        log(f"  EPE of the timed GPU path vs the CPU oracle on the same pair: {epe:.3e} px")
+        cpu["epe_gpu_vs_cpu_px"] = epe
+    strict = None
+    if n_gpus == 1 and args.dtype == "f32" and rag_amd.ops.get_conv_precision() == "f16x3":
+        # the same workload with every contraction on the fp32-input MFMA forms: the record carries both arithmetic contracts
+        with rag_amd.ops.conv_precision("fp32"):
+            for _ in range(2):
+                out32 = step()
+            torch.cuda.synchronize()
+            g32, cap32 = try_capture(step) if args.graph else (None, None)
+            n32 = min(args.steps, 10)
+            ramp(g32)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n32):
+                if g32 is not None:
+                    g32.replay()
+                else:
+                    out32 = step()
+            torch.cuda.synchronize()
+            dt32 = (time.perf_counter() - t0) / n32
+            out32 = cap32 if g32 is not None else out32
+            # its own roofline: per-kernel HIP events of an eager pass of the same kernels under the strict contract
+            prof.records.clear()
+            prof.enabled = True
+            for _ in range(n32):
+                step()
+            torch.cuda.synchronize()
+            prof.enabled = False
+            strict_roofline = roofline_of(prof.summary(), args, dt32 * n32, g32 is not None, steps=n32)
+        strict = {"value_fp32_mfma": round(B / dt32, 3), "ms_per_step": round(dt32 * 1e3, 4), "steps": n32,
+                  "what": "same workload, ops.set_conv_precision('fp32'): every 3x3x3 contraction on v_mfma_f32_4x4x1 (exact fmaf chains)",
+                  "roofline": strict_roofline}
+        if cpu is not None:
+            strict["epe_gpu_vs_cpu_px"] = O.epe(out32[:1].float().cpu(), ref)
+        log(f"  strict fp32 MFMA: {strict['value_fp32_mfma']} maps/s, EPE {strict.get('epe_gpu_vs_cpu_px')}")
+    epe_bf16_vs_fp32 = None
+    if n_gpus == 1 and args.dtype == "bf16":
+        with torch.no_grad():
+            d32 = net(lf[:1].float(), rf[:1].float())
+        epe_bf16_vs_fp32 = float((out[:1].double() - d32.double()).abs().flatten(1).mean(dim=1).mean())
+        log(f"  EPE bf16 storage vs the fp32 build on the same pair: {epe_bf16_vs_fp32:.3e} px")
+    e2e = None
+    if n_gpus == 1 and args.dtype == "f32":
+        try:      # a rider: it must never cost the headline its line
+            e2e = end_to_end(device, min(args.steps, 10), use_graph=bool(args.graph))
+        except Exception as exc:  # noqa: BLE001
+            log(f"bench: end_to_end leg failed ({type(exc).__name__}: {exc})")
+            e2e = {"error": f"{type(exc).__name__}: {exc}"}
+            safe_sync()
+    if e2e and "value" in e2e:
+        log(f"  end-to-end (images -> disparity, Feature Net + Matching Net): {e2e['value']} maps/s ({e2e['ms_per_pair']} ms/pair)")
+    configs = None
+    if (n_gpus == 1 and args.dtype == "f32" and B == 1 and (H, W) == (384, 1248) and not args.no_configs):
+        try:      # the riders must never cost the headline its line
+            configs = other_configs(net, lf, rf, out, ref if cpu is not None else None, device, bool(args.graph), dist)
+        except Exception as exc:  # noqa: BLE001
+            log(f"bench: the legs of the other configurations failed ({type(exc).__name__}: {exc})")
+            configs = {"error": f"{type(exc).__name__}: {exc}"}
+            safe_sync()
+    return {"roofline": roofline, "cpu_baseline": cpu, "strict_fp32": strict, "epe_bf16_vs_fp32": epe_bf16_vs_fp32,
+            "end_to_end": e2e, "configs": configs}
 
 
 def rank_env(args_gpus: int):
@@ -778,18 +918,25 @@ def main():
                     help="1 (default): replay the step as a captured hipGraph; 0: eager launches")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="activation storage: f32 (configs[1], default) or bf16 storage / fp32 accumulate (configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--train", action="store_true", help="BASELINE configs[4]: time the data-parallel training step instead")
     ap.add_argument("--train-precision", choices=["fp32", "f16x3"], default="fp32",
                     help="arithmetic of the training step's 3x3x3 convolutions: fp32 (default, the reference's class) or f16x3 (opt-in)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the legs of the other BASELINE configurations (configs object)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the legs of the other BASELINE configurations (configs object)")
     ap.add_argument("--hw", default=None, help="HxW of the stereo pairs, multiples of 12 (default 384x1248 = configs[1]; configs[3]: "
                                                "480x960 with --batch 8)")
     ap.add_argument("--precision", choices=["f16x3", "fp32"], default=None,
                     help="arithmetic contract of the 3x3x3 convolutions of the TIMED path (default: the library's default, f16x3); fp32 = "
                          "the strict leg as the headline (profiling passes of the strict path: tools/collect_profiles.sh)")
     ap.add_argument("--dry-ranks", action="store_true", help="rank plumbing only (no GPU): every rank reports rank / world / device / seed")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: roofline, cpu_baseline, "
+                         "strict_fp32, epe_bf16_vs_fp32, end_to_end, configs (--train: phases, roofline, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32, 64 MB at most)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: be the launcher (before anything touches the GPU: `import torch` above makes no HIP call)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -822,9 +969,9 @@ def main():
         rag_amd.ops.set_conv_precision(args.precision)
     if args.train:
         line = train_leg(device, dist, rank, n_gpus, args.batch if args.batch > 1 else TRAIN_B, args.steps, args.warmup, bool(args.graph),
-                         args.train_precision, with_cpu=not args.no_cpu_baseline)
+                         args.train_precision, with_cpu=not args.no_cpu_baseline, full=args.full, dump_dir=args.dump_outputs)
         if line is not None:
-            line["library"] = rag_amd.lib_path()
+            line["full"], line["library"] = args.full, rag_amd.lib_path()
             print(json.dumps(line), flush=True)
         if dist is not None:
             dist.barrier()
@@ -862,116 +1009,19 @@ def main():
         else:
             holder["out"] = step()
 
-    prof.enabled = graph is None and rank == 0
+    prof.enabled = args.full and graph is None and rank == 0
     # (the W warm-up steps ran above, eagerly: one-time costs; the replays below are the clock ramp, RAMP_REPLAYS above)
     dt = timed_region(timed_step, args.steps, RAMP_REPLAYS if graph is not None else 0, dist, torch.cuda.synchronize, device)
     prof.enabled = False
     out = holder.get("out", out)
 
-    if graph is not None and rank == 0:   # per-kernel events need eager launches: same kernels, extra pass
-        prof.enabled = True
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        prof.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"disparity": out})
 
     if rank == 0:
-        torch.cuda.synchronize()
-        by = prof.summary()
-        roofline = roofline_of(by, args, dt, graph is not None)
-        if graph is not None and roofline and roofline["kernel"].startswith("conv3d_x3") and "<2," in roofline["kernel"]:
-            # the dominant kernel = the level-3 dual launches: their times INSIDE a replayed graph (dual_launches_in_graph_us) replace the
-            # eager-pass figure in `achieved` / `frac`; the eager one stays beside it
-            try:
-                with torch.no_grad():
-                    us = dual_launches_in_graph_us(step, (MAXDISP // 3, H // 3, W // 3))
-            except Exception as exc:      # noqa: BLE001 (a measurement aid: never fatal)
-                log(f"bench: in-graph launch timing failed ({type(exc).__name__}: {exc})")
-                us = []
-            if us and len(us) == roofline["launches_per_step"]:
-                avg = sum(us) / len(us)
-                roofline["avg_launch_us_eager"] = roofline["avg_launch_us"]
-                roofline["avg_launch_us"] = round(avg, 2)
-                roofline["launch_us_in_graph"] = [round(u, 1) for u in us]
-                roofline["avg_launch_us_source"] = ("HIP events on the launch stream around back-to-back replays of a captured hipGraph holding 20 launches "
-                                                    "of each of this forward's level-3 dual launches with their own buffers (per-kernel events cannot be "
-                                                    "recorded inside a graph on this runtime; events around eager launches — avg_launch_us_eager — read "
-                                                    "10-20 % long); rocprofv3's averages of the replayed graph agree: profiles/r05*_step_timeline.txt")
-                if roofline["bound"] == "hbm":
-                    gbs = roofline["algorithmic_bytes_per_launch"] / (avg * 1e-6) * 1e-9
-                    roofline["achieved"], roofline["frac"] = round(gbs, 1), round(gbs / PEAK_HBM_GBS, 4)
-                    tf = roofline["flops_per_launch"] / (avg * 1e-6) * 1e-12
-                    roofline["mfma"]["achieved_tflops"], roofline["mfma"]["frac"] = round(tf, 2), round(tf / roofline["mfma"]["peak"], 4)
-                roofline["share_of_step"] = round(sum(us) * 1e-6 / (dt / args.steps), 3)
-        if by:
-            for k, (s_, f_, b_, n_) in sorted(by.items(), key=lambda kv: -kv[1][0]):
-                log(f"  conv3d {'x3 (split operands) channel groups' if k[1] == 'x3' else 'k3 G'}={k[0]} tx={k[1]} R={k[2]} nset={k[3]}: {n_ // args.steps} launches/step, {s_ / args.steps * 1e3:.3f} ms/step, "
-                    f"{f_ / s_ * 1e-12:.1f} TFLOP/s, {b_ / s_ * 1e-9:.0f} GB/s (in+out)")
-        cpu = None
-        if n_gpus == 1 and not args.no_cpu_baseline:
-            cpu, ref = cpu_baseline(net, lf.float(), rf.float())
-            from oracle import matching_oracle as O
-            epe = O.epe(out[:1].float().cpu(), ref)
-            log(f"  EPE of the timed GPU path vs the CPU oracle on the same pair: {epe:.3e} px")
-            cpu["epe_gpu_vs_cpu_px"] = epe
-        strict = None
-        if n_gpus == 1 and args.dtype == "f32" and rag_amd.ops.get_conv_precision() == "f16x3":
-            # the same workload with every contraction on the fp32-input MFMA forms: the record carries both arithmetic contracts
-            with rag_amd.ops.conv_precision("fp32"):
-                for _ in range(2):
-                    out32 = step()
-                torch.cuda.synchronize()
-                g32, cap32 = try_capture(step) if args.graph else (None, None)
-                n32 = min(args.steps, 10)
-                ramp(g32)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(n32):
-                    if g32 is not None:
-                        g32.replay()
-                    else:
-                        out32 = step()
-                torch.cuda.synchronize()
-                dt32 = (time.perf_counter() - t0) / n32
-                out32 = cap32 if g32 is not None else out32
-                # its own roofline: per-kernel HIP events of an eager pass of the same kernels under the strict contract
-                prof.records.clear()
-                prof.enabled = True
-                for _ in range(n32):
-                    step()
-                torch.cuda.synchronize()
-                prof.enabled = False
-                strict_roofline = roofline_of(prof.summary(), args, dt32 * n32, g32 is not None, steps=n32)
-            strict = {"value_fp32_mfma": round(B / dt32, 3), "ms_per_step": round(dt32 * 1e3, 4), "steps": n32,
-                      "what": "same workload, ops.set_conv_precision('fp32'): every 3x3x3 contraction on v_mfma_f32_4x4x1 (exact fmaf chains)",
-                      "roofline": strict_roofline}
-            if cpu is not None:
-                strict["epe_gpu_vs_cpu_px"] = O.epe(out32[:1].float().cpu(), ref)
-            log(f"  strict fp32 MFMA: {strict['value_fp32_mfma']} maps/s, EPE {strict.get('epe_gpu_vs_cpu_px')}")
-        epe_bf16_vs_fp32 = None
-        if n_gpus == 1 and args.dtype == "bf16":
-            with torch.no_grad():
-                d32 = net(lf[:1].float(), rf[:1].float())
-            epe_bf16_vs_fp32 = float((out[:1].double() - d32.double()).abs().flatten(1).mean(dim=1).mean())
-            log(f"  EPE bf16 storage vs the fp32 build on the same pair: {epe_bf16_vs_fp32:.3e} px")
-        e2e = None
-        if n_gpus == 1 and args.dtype == "f32":
-            try:      # a rider: it must never cost the headline its line
-                e2e = end_to_end(device, min(args.steps, 10), use_graph=bool(args.graph))
-            except Exception as exc:  # noqa: BLE001
-                log(f"bench: end_to_end leg failed ({type(exc).__name__}: {exc})")
-                e2e = {"error": f"{type(exc).__name__}: {exc}"}
-                safe_sync()
-        if e2e and "value" in e2e:
-            log(f"  end-to-end (images -> disparity, Feature Net + Matching Net): {e2e['value']} maps/s ({e2e['ms_per_pair']} ms/pair)")
-        configs = None
-        if (n_gpus == 1 and args.dtype == "f32" and B == 1 and (H, W) == (384, 1248) and not args.no_configs):
-            try:      # the riders must never cost the headline its line
-                configs = other_configs(net, lf, rf, out, ref if cpu is not None else None, device, bool(args.graph), dist)
-            except Exception as exc:  # noqa: BLE001
-                log(f"bench: the legs of the other configurations failed ({type(exc).__name__}: {exc})")
-                configs = {"error": f"{type(exc).__name__}: {exc}"}
-                safe_sync()
+        riders = dict.fromkeys(("roofline", "cpu_baseline", "strict_fp32", "epe_bf16_vs_fp32", "end_to_end", "configs"))
+        if args.full:
+            riders = full_riders(args, net, step, lf, rf, out, dt, graph, prof, device, dist, n_gpus, B)
         ms = dt / args.steps * 1e3
         line = {
             "metric": f"disparity maps/sec at {H}x{W} D=192 (Matching-Net forward)",
@@ -992,8 +1042,7 @@ def main():
                                          if graph is not None else f"{max(args.warmup, 1)} eager steps"),
                        "ranks_seen": dist.get_world_size() if dist is not None else 1,
                        "dist_backend": dist.get_backend() if dist is not None else None},
-            "roofline": roofline, "cpu_baseline": cpu, "strict_fp32": strict, "epe_bf16_vs_fp32": epe_bf16_vs_fp32, "end_to_end": e2e,
-            "configs": configs, "library": rag_amd.lib_path(), "graph_nodes": graph_nodes or None,
+            **riders, "full": args.full, "library": rag_amd.lib_path(), "graph_nodes": graph_nodes or None,
         }
         if GPU_ERROR:
             line["gpu_error"] = GPU_ERROR

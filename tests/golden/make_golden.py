@@ -55,6 +55,21 @@ def sd_np(module, prefix="sd::"):
 ONLY = [a for a in sys.argv[1:] if not a.startswith("-")]   # e.g. `make_golden.py g8` regenerates one fixture family
 
 
+def forward_f64(net, feas, fn):
+    """fn(copy of `net` in float64) under no_grad, with the Feature Net's outputs (last_3_2d) replaced by `feas` (stored float32
+    features, cast to double, in call order): the Matching-Net half alone, as the oracle tests feed it."""
+    import copy
+    net64 = copy.deepcopy(net).double()
+    queue = [torch.from_numpy(f).double() for f in feas]
+    hk = [m.register_forward_hook(lambda _m, _i, _o: queue.pop(0)) for m in net64.last_3_2d]
+    with torch.no_grad():
+        out = fn(net64).numpy()
+    for h_ in hk:
+        h_.remove()
+    assert not queue
+    return out
+
+
 def save(name, **arrays):
     if ONLY and not any(name.startswith(o) for o in ONLY):
         return
@@ -189,6 +204,15 @@ def main():
                   "mat": cap["mat"].numpy(), "disp": disp.numpy(), "rows": rows, "maxdisp": np.int64(D)}
         arrays.update(sd_np(net))
         save("g5_forward_" + name, **arrays)
+        # mat and disp in float64 from the same stored features and weights (see G10's float64 outputs below for why)
+        cap64 = {}
+
+        def run64(n_):
+            n_.disp.register_forward_pre_hook(lambda m, inp: cap64.__setitem__("mat", inp[0].clone()))
+            return n_.forward(left.double(), right.double(), 0, n_.arch_init)
+
+        disp64 = forward_f64(net, (arrays["left_fea"], arrays["right_fea"]), run64)
+        save("g5_forward_" + name + "_f64", mat=cap64["mat"].numpy(), disp=disp64)
 
     # ---- G6: one fwd+bwd training step as in approaches/rag.py:155-219 (smooth-L1 on 0<gt<192 mask)
     net = network(ALL_CONV, 24, 61)
@@ -335,6 +359,13 @@ def main():
             del feas[:]
             arrays[f"search_disp_{tag}"] = net.search_forward(left, right, t, sel).numpy()
             arrays[f"search_left_fea_{tag}"], arrays[f"search_right_fea_{tag}"] = feas[0].numpy(), feas[1].numpy()
+    # the same outputs in float64 from the same stored features and weights (g10_grown_model_f64; g5 likewise): at random weights the
+    # float32 forward is ill-conditioned (|cost| ~1e4, softmin nearly an argmin), so its last bits — the summation order of the
+    # host's BLAS, which differs between CPU models — move single pixels by up to ~0.05 px; in float64 they do not
+    f64 = {}
+    for tag, sel, t in (("a", sel_a, 1), ("b", sel_b, 1), ("c", sel_a, 0)):
+        f64[f"search_disp_{tag}"] = forward_f64(net, (arrays[f"search_left_fea_{tag}"], arrays[f"search_right_fea_{tag}"]),
+                                                lambda n_, sel=sel, t=t: n_.search_forward(left.double(), right.double(), t, sel))
     winners = (1, 3, 5, 7, 9, 11, 12, 15, 17)           # p-indices where the candidate wins (2-D and 3-D layers, both stems kinds)
     for k_, p_ in enumerate(net.p):
         if k_ in winners:
@@ -347,6 +378,10 @@ def main():
             del feas[:]
             arrays[f"disp_t{t}"] = net.forward(left, right, t, arch).numpy()
             arrays[f"left_fea_t{t}"], arrays[f"right_fea_t{t}"] = feas[0].numpy(), feas[1].numpy()
+    for t, arch in ((0, arch0), (1, best)):
+        f64[f"disp_t{t}"] = forward_f64(net, (arrays[f"left_fea_t{t}"], arrays[f"right_fea_t{t}"]),
+                                        lambda n_, t=t, arch=arch: n_.forward(left.double(), right.double(), t, arch))
+    save("g10_grown_model_f64", **f64)
     for h_ in hk:
         h_.remove()
     blob = {"arch_t0": arch0, "arch_t1": best, "winners": list(winners), "length": {k_: int(v) for k_, v in net.length.items()}}

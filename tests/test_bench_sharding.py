@@ -1,5 +1,6 @@
 """Multi-rank logic of bench.py on CPU: 2 processes, gloo backend.  The data path has no collective (pairs are
-independent); what is distributed is the batch split and the max-over-ranks timing."""
+independent); what is distributed is the batch split and the max-over-ranks timing.  At the end: the command line of a plain
+run (--steps, --dump-outputs)."""
 import os
 import sys
 import time
@@ -152,3 +153,38 @@ def test_bench_launcher_reports_a_failed_rank():
     """A child that dies makes the launcher exit non-zero (rank 1 exits before the group forms; rank 0's rendezvous then fails too)."""
     r = _run_bench("--gpus", "2", "--dry-ranks", env={"RAGMI_BENCH_DRY_FAIL_RANK": "1", "TORCH_DIST_INIT_BARRIER": "0"})
     assert r.returncode != 0
+
+
+def test_bench_rejects_zero_steps():
+    r = _run_bench("--steps", "0", "--dry-ranks")
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_outputs_float32_and_a_fixed_sample_above_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; an array above its share of the cap becomes the same seeded sample on every run."""
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * (4096 + 4 * 100))       # 100 elements per array
+    x = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"big": x, "small": torch.ones(3, dtype=torch.bfloat16)})
+    big = np.load(tmp_path / "a" / "big.npy")
+    assert big.dtype == np.float32 and big.shape == (100,)
+    assert np.all(np.diff(big) > 0) and set(big.tolist()) <= set(range(1000))
+    np.testing.assert_array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+    small = np.load(tmp_path / "a" / "small.npy")
+    assert small.dtype == np.float32 and small.tolist() == [1.0, 1.0, 1.0]
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_the_disparity(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full): K timed steps, ms_per_step = 1 / value for one pair, no rider
+    objects, and --dump-outputs writes the last timed step's disparity [1, 384, 1248] as float32."""
+    import json
+    r = _run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "disparity maps/s"
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-2
+    assert all(d[k] is None for k in ("roofline", "cpu_baseline", "strict_fp32", "epe_bf16_vs_fp32", "end_to_end", "configs"))
+    disp = np.load(tmp_path / "disparity.npy")
+    assert disp.dtype == np.float32 and disp.shape == (1, 384, 1248)
+    assert np.isfinite(disp).all() and disp.min() >= -1e-3 and disp.max() <= 192

@@ -3,7 +3,7 @@
 n=$1; extra=$2; shift 2
 for i in $(seq 1 "$n"); do
   for lib in "$@"; do
-    RAG_AMD_LIB=$(realpath "$lib") python bench.py --no-cpu-baseline --no-configs --steps 30 $extra 2>/tmp/ab_err.txt | python -c "
+    RAG_AMD_LIB=$(realpath "$lib") python bench.py --full --no-cpu-baseline --no-configs --steps 30 $extra 2>/tmp/ab_err.txt | python -c "
 import json,sys
 s=sys.stdin.read()
 try:

@@ -3,7 +3,7 @@
 var=$1; a=$2; b=$3; n=${4:-3}; extra=${5:-}
 for i in $(seq 1 "$n"); do
   for val in "$a" "$b"; do
-    env "$var=$val" python bench.py --no-cpu-baseline --no-configs --steps 30 $extra 2>/tmp/ab_err.txt | python -c "
+    env "$var=$val" python bench.py --full --no-cpu-baseline --no-configs --steps 30 $extra 2>/tmp/ab_err.txt | python -c "
 import json,sys
 s=sys.stdin.read()
 try:

@@ -1,6 +1,6 @@
 """Kernel-by-kernel timeline of ONE headline forward pass from a rocprofv3 kernel trace.
 
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline
+    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline
     python tools/step_timeline.py <dir> > profiles/rNN_step_timeline.txt
 
 The pass is found as the last run of dispatches that starts with costvol_stem_planes_mfma_kernel (the headline's first kernel under
