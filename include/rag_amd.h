@@ -543,6 +543,28 @@ int ragmi_stereo_metrics_fwd(const void* disp_est, const void* disp_gt, int B, i
 int ragmi_masked_smooth_l1_bwd(const void* disp_est, const void* disp_gt, const void* out, const void* gout, void* ddisp,
                                int B, int H, int W, float maxdisp, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Self-supervised loss of the continual-adaptation mode (src_self/approaches/rag.py:266-278, supervise=False):
+ * re_and_sm_loss(disp, left, right) of src_self/models/loss.py:112-141 and its gradient with respect to disp.
+ *   left_est[c] = m * bilinear(right[c], xs, ys), xs = ((2 (x - d)/(W-1) - 1 + 1) W - 1)/2, ys = ((2 y/(H-1) - 1 + 1) H - 1)/2
+ *                 (warp, loss.py:6-37: align_corners=True normalisation, grid_sample's default align_corners=False, zero padding);
+ *                 m = 1 where the same sample of an all-ones image is >= 0.9999, else 0 (no gradient through m);
+ *   out[1] = SSIM_mean: clamp((1 - S)/2, 0, 1) over the non-overlapping 3x3 blocks of avg_pool2d(kernel_size=3) (loss.py:77-97;
+ *            the H%3 / W%3 remainder takes no part), C1 = 1e-4, C2 = 9e-4, sigma = E[x^2] - mu^2;
+ *   out[2] = L1_mean: mean |left - left_est| over B*C*H*W (loss.py:64-75);
+ *   out[3] = smoothness: sum over x-edges |d(x) - d(x+1)| exp(-|mean_c(left(x) - left(x+1))|) + the same over y-edges, / (B*H*W)
+ *            (loss.py:122-139);
+ *   out[0] = 0.85 out[1] + 0.15 out[2] + 0.1 out[3].
+ * left, right: [B,C,H,W], disp: [B,H,W], all fp32 (dtype must be RAGMI_F32), C in 1..4, H, W >= 3; out: 4 floats; workspace:
+ * ragmi_selfsup_loss_workspace_elems(B,H,W) floats, 8-byte aligned, scratch.  unit_grad (may be NULL: no gradient work) receives
+ * d out[0] / d disp, [B,H,W].  Two launches, no atomics (bitwise reproducible), no memset, no host synchronisation. */
+int64_t ragmi_selfsup_loss_workspace_elems(int B, int H, int W);
+int ragmi_selfsup_loss_fwd(const void* left, const void* right, const void* disp, int B, int C, int H, int W, int dtype,
+                           void* workspace, void* out, void* unit_grad, void* stream);
+
+/* backward of ragmi_selfsup_loss_fwd's out[0]: grad[i] = gout[0] * unit_grad[i], i < n (gout read on the device) */
+int ragmi_selfsup_loss_bwd(const void* unit_grad, const void* gout, void* grad, int64_t n, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * clip_grad_norm_(max_norm) + torch.optim.SGD(lr, momentum, weight_decay).step() over flat fp32 buffers of n elements
  * (approaches/rag.py:64-70, 215-216) as two launches: g *= min(1, max_norm/(||g||+1e-6)) (max_norm <= 0: no clipping);

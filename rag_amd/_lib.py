@@ -131,6 +131,10 @@ SIGNATURES = {
     "ragmi_disparity_regression_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_stereo_metrics_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "ragmi_masked_smooth_l1_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "ragmi_selfsup_loss_workspace_elems": (c_int64, [c_int, c_int, c_int]),
+    "ragmi_selfsup_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "ragmi_selfsup_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ragmi_disp_softargmin_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_disp_softargmin_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p]),

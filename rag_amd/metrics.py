@@ -76,3 +76,91 @@ class MaskedSmoothL1Fn(torch.autograd.Function):
 
 def masked_smooth_l1(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float = 192) -> torch.Tensor:
     return MaskedSmoothL1Fn.apply(disp_est, disp_gt, maxdisp)
+
+
+# --------------------------------------------------------------------------- self-supervised loss (src_self, supervise=False)
+SELFSUP_NAMES = ("loss", "ssim", "l1", "smooth")
+
+
+def _selfsup_raw(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor, want_grad: bool):
+    """(out[4], unit gradient or None) of ragmi_selfsup_loss_fwd; nothing leaves the device."""
+    for t in (disp_est, left, right):
+        if not t.is_cuda:
+            raise RuntimeError("rag_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
+    if disp_est.dim() != 3 or left.dim() != 4 or right.shape != left.shape or left.shape[0] != disp_est.shape[0] \
+            or tuple(left.shape[2:]) != tuple(disp_est.shape[1:]):
+        raise ValueError("re_and_sm_loss: disp_est must be [B, H, W] and left, right [B, C, H, W]")
+    dtypes = {disp_est.dtype, left.dtype, right.dtype}
+    dt = ops._DT.get(disp_est.dtype, -1) if len(dtypes) == 1 else -1     # the library refuses what it was not built for
+    B, C, H, W = left.shape
+    d, lt, rt = disp_est.contiguous(), left.contiguous(), right.contiguous()
+    lib = load_library()
+    ws = torch.empty((max(1, lib.ragmi_selfsup_loss_workspace_elems(B, H, W)),), device=d.device, dtype=torch.float32)
+    out = torch.empty((4,), device=d.device, dtype=torch.float32)
+    ug = torch.empty((B, H, W), device=d.device, dtype=torch.float32) if want_grad else None
+    check(lib.ragmi_selfsup_loss_fwd(lt.data_ptr(), rt.data_ptr(), d.data_ptr(), B, C, H, W, dt, ws.data_ptr(), out.data_ptr(),
+                                     ug.data_ptr() if ug is not None else None, ops._stream()), "selfsup_loss_fwd")
+    return out, ug
+
+
+class SelfSupervisedLossFn(torch.autograd.Function):
+    """re_and_sm_loss (src_self/models/loss.py:112-141) of disp_est [B,H,W] against the images it was computed from: one fused
+    forward that also writes d loss / d disp_est at unit scale, and a backward that scales it by the incoming gradient.  Images get
+    no gradient (the reference's step never asks for one)."""
+
+    @staticmethod
+    def forward(ctx, disp_est, left, right):
+        out, ug = _selfsup_raw(disp_est.detach(), left.detach(), right.detach(), ctx.needs_input_grad[0])
+        if ug is not None:
+            ctx.save_for_backward(ug)
+        return out[0] * 1.0          # a kernel, not a memcpy node (as MaskedSmoothL1Fn)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (ug,) = ctx.saved_tensors
+        gout = gout.reshape(1).contiguous().float()
+        g = torch.empty_like(ug)
+        check(load_library().ragmi_selfsup_loss_bwd(ug.data_ptr(), gout.data_ptr(), g.data_ptr(), ug.numel(), ops._stream()),
+              "selfsup_loss_bwd")
+        return g, None, None
+
+
+def re_and_sm_loss(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+    """The self-supervised training loss of src_self (models/loss.py:112-141) under the reference's name: 0.85 SSIM + 0.15 L1
+    of `right` warped to `left` by disp_est, + 0.1 edge-aware smoothness; differentiable in disp_est (HIP, fp32)."""
+    return SelfSupervisedLossFn.apply(disp_est, left, right)
+
+
+def self_supervised_terms(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+    """The 4-float device vector (loss, SSIM_mean, L1_mean, smoothness) of re_and_sm_loss for logging: no gradient, no sync."""
+    with torch.no_grad():
+        return _selfsup_raw(disp_est.detach(), left.detach(), right.detach(), False)[0]
+
+
+def re_and_sm_loss_torch(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor):
+    """Plain-torch restatement of re_and_sm_loss in the dtype and on the device of its inputs (host twin of the CPU step, and the
+    fp64 / ATen yardstick of the tests and tools/bench_selfsup.py).  Returns (loss, (ssim_mean, l1_mean, smooth_mean))."""
+    import torch.nn.functional as F
+    B, C, H, W = left.shape
+    dt, dev = disp_est.dtype, disp_est.device
+    xs = torch.arange(W, device=dev, dtype=dt).view(1, 1, W) - disp_est
+    ys = torch.arange(H, device=dev, dtype=dt).view(1, H, 1).expand(B, H, W)
+    grid = torch.stack((2 * xs / (W - 1) - 1, 2 * ys / (H - 1) - 1), dim=-1)      # align_corners=True normalisation ...
+    sample = F.grid_sample(right, grid, mode="bilinear", padding_mode="zeros", align_corners=False)   # ... sampled without it
+    with torch.no_grad():
+        cover = F.grid_sample(torch.ones_like(right[:, :1]), grid.detach(), mode="bilinear", padding_mode="zeros", align_corners=False)
+        keep = (cover >= 0.9999).to(dt)
+    est = sample * keep
+    l1 = (left - est).abs().mean()
+    mu_x, mu_y = F.avg_pool2d(left, 3), F.avg_pool2d(est, 3)                    # stride 3: non-overlapping blocks
+    var_x = F.avg_pool2d(left * left, 3) - mu_x * mu_x
+    var_y = F.avg_pool2d(est * est, 3) - mu_y * mu_y
+    cov = F.avg_pool2d(left * est, 3) - mu_x * mu_y
+    c1, c2 = 1e-4, 9e-4
+    s = (2 * mu_x * mu_y + c1) * (2 * cov + c2) / ((mu_x * mu_x + mu_y * mu_y + c1) * (var_x + var_y + c2))
+    ssim = torch.clamp((1 - s) / 2, 0, 1).mean()
+    wx = torch.exp(-(left[..., :, :-1] - left[..., :, 1:]).mean(1).abs())
+    wy = torch.exp(-(left[..., :-1, :] - left[..., 1:, :]).mean(1).abs())
+    smooth = (((disp_est[..., :, :-1] - disp_est[..., :, 1:]).abs() * wx).sum()
+              + ((disp_est[..., :-1, :] - disp_est[..., 1:, :]).abs() * wy).sum()) / (B * H * W)
+    return 0.85 * ssim + 0.15 * l1 + 0.1 * smooth, (ssim, l1, smooth)

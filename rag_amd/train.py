@@ -71,19 +71,39 @@ def masked_smooth_l1(disp: torch.Tensor, gt: torch.Tensor, maxdisp: int) -> torc
     return (per * mask).sum() / mask.sum()
 
 
+def self_supervised_loss(disp: torch.Tensor, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+    """re_and_sm_loss(disp, left, right) of src_self/models/loss.py:112-141, the loss of the supervise=False step
+    (src_self/approaches/rag.py:270-278): the fused HIP loss of rag_amd.metrics on the GPU."""
+    if disp.is_cuda:
+        from .metrics import re_and_sm_loss as fused
+        return fused(disp, left, right)
+    from .metrics import re_and_sm_loss_torch           # host-side twin (CPU tests of the step logic)
+    return re_and_sm_loss_torch(disp, left, right)[0]
+
+
+def _check_supervision(gt, features: bool, supervise: bool) -> None:
+    if not supervise and features:
+        raise ValueError("supervise=False needs the images (the loss warps the right image onto the left): features=True is refused")
+    if supervise and gt is None:
+        raise ValueError("supervise=True needs the ground-truth disparity gt")
+
+
 TRAIN_PRECISION = "fp32"     # the reference's training step is fp32 (rag.py:204-216); "f16x3" is opt-in (~6 % of the step)
 
 
 def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None, features: bool = False,
-                     precision: Optional[str] = None):
-    """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  `features=True`: `net` is a
+                     precision: Optional[str] = None, supervise: bool = True):
+    """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  `supervise=False`: the self-supervised loss
+    re_and_sm_loss(disp, left, right) of src_self (approaches/rag.py:270-278) instead, `gt` may be None, and left/right must be
+    the images (features=True raises ValueError).  `features=True`: `net` is a
     MatchingNet and left/right are Feature-Net outputs.  `precision`: arithmetic of the 3x3x3 convolutions of the step (forward and
     data gradient): "fp32" (default, TRAIN_PRECISION: every contraction on the fp32-input MFMA forms, the reference's arithmetic
     class) or "f16x3" (opt-in; bound in include/rag_amd.h).  Returns the (detached) loss."""
+    _check_supervision(gt, features, supervise)
     from . import ops
     with ops.conv_precision(precision or TRAIN_PRECISION):
         disp = net(left, right, task_arch) if features else net(left, right, 0, task_arch if task_arch is not None else net.arch_init)
-        loss = masked_smooth_l1(disp, gt, net.maxdisp)
+        loss = masked_smooth_l1(disp, gt, net.maxdisp) if supervise else self_supervised_loss(disp, left, right)
         bucket.zero()
         loss.backward()
     return loss.detach()
@@ -147,10 +167,11 @@ def exchange_and_update(optimizer, bucket: GradBucket, *, clip: float = 5.0, dis
 
 
 def train_step(net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
-               features: bool = False, precision: Optional[str] = None):
-    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision` as in forward_backward (default fp32).
-    Returns the (detached) loss."""
-    loss = forward_backward(net, bucket, left, right, gt, task_arch=task_arch, features=features, precision=precision)
+               features: bool = False, precision: Optional[str] = None, supervise: bool = True):
+    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision` and `supervise` as in forward_backward
+    (defaults: fp32, supervised).  Returns the (detached) loss."""
+    loss = forward_backward(net, bucket, left, right, gt, task_arch=task_arch, features=features, precision=precision,
+                            supervise=supervise)
     exchange_and_update(optimizer, bucket, clip=clip, dist=dist)
     return loss
 
@@ -180,14 +201,16 @@ class GraphedTrainStep:
     is not established, so the invariant is ENFORCED rather than assumed: the captured graph's nodes are counted at capture time
     (ragmi_graph_node_census) and a capture holding any memcpy / memset node is refused — an ATen op that starts lowering to
     copy_ or memset after a torch upgrade fails loudly here instead of corrupting a replay.  The graph replays on the caller's
-    current stream; no private stream is involved."""
+    current stream; no private stream is involved.  `supervise=False`: the self-supervised step of src_self (gt may be None)."""
 
     def __init__(self, net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
-                 features: bool = False, warmup: int = 2, precision: Optional[str] = None):
+                 features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True):
+        _check_supervision(gt, features, supervise)
         self.net, self.opt, self.bucket, self.clip, self.dist = net, optimizer, bucket, clip, dist
-        self.left, self.right, self.gt = left.clone(), right.clone(), gt.clone()
+        self.left, self.right = left.clone(), right.clone()
+        self.gt = gt.clone() if gt is not None else None
         self.precision = precision or TRAIN_PRECISION
-        kw = dict(task_arch=task_arch, features=features, precision=self.precision)
+        kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                  # warm-up on a side stream: lazy state (allocator pools, occupancy
@@ -215,7 +238,7 @@ class GraphedTrainStep:
 
     def __call__(self, left=None, right=None, gt=None):
         for dst, src in ((self.left, left), (self.right, right), (self.gt, gt)):
-            if src is not None and src.data_ptr() != dst.data_ptr():
+            if src is not None and dst is not None and src.data_ptr() != dst.data_ptr():
                 dst.copy_(src)
         self.graph.replay()
         if self._bn_buffers:
