@@ -565,6 +565,30 @@ int ragmi_selfsup_loss_fwd(const void* left, const void* right, const void* disp
 /* backward of ragmi_selfsup_loss_fwd's out[0]: grad[i] = gout[0] * unit_grad[i], i < n (gout read on the device) */
 int ragmi_selfsup_loss_bwd(const void* unit_grad, const void* gout, void* grad, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Depth head of the monocular-depth network (rag_depth/src/models/rag_model.py:51-64, 357-416) as ONE launch:
+ *   u   = bilinear(y, (H, W), align_corners=True)                      (upsample_6)
+ *   m   = conv3x3(u, w3[1, Cin, 3, 3]), zero padding 1, no bias         (last_3_3d: bn=False, relu=False)
+ *   s   = sigmoid(conv3x3(m, w1[1, 1, 3, 3]) + b1[0]), zero padding 1   (DispHead.conv1 + sigmoid)
+ *   out = max_depth * bilinear(s, x scale, align_corners=False)        (F.interpolate(scale_factor=scale); source index clamped)
+ * y: [B, Cin, Hi, Wi] contiguous, out: [B, scale*H, scale*W]; w3, w1, b1 are device pointers (b1 is never read on the host).
+ * fp32 only (dtype must be RAGMI_F32); Cin 1..16, Hi <= H, Wi <= W, scale 1..8 (ragmi_depth_head_supported returns 1 for a built
+ * combination).  No allocation, no host synchronisation. */
+int ragmi_depth_head_supported(int Cin, int Hi, int Wi, int H, int W, int scale, int dtype);
+int ragmi_depth_head_fwd(const void* y, const void* w3, const void* w1, const void* b1, void* out, int B, int Cin, int Hi, int Wi,
+                         int H, int W, int scale, float max_depth, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Depth loss + evaluation metrics in one pass (rag_depth/src/approaches/rag.py:440-489) over the n pixels of (est, gt) with
+ * gt > 0, the whole batch together.  out10 = silog_loss (sqrt(mean d^2 - variance_focus mean(d)^2) * 10, d = log est - log gt,
+ * utilstool/experiment.py:154-161), then compute_errors (approaches/rag.py:19-41): silog, abs_rel, log10, rms, sq_rel, log_rms,
+ * d1, d2, d3.  No clamping: est == 0 or no masked pixel gives the reference's inf / NaN.  workspace:
+ * ragmi_depth_metrics_workspace_elems(n) floats, 8-byte aligned, scratch.  fp32 only.  Two launches, no atomics (bitwise
+ * reproducible), no memset, no host synchronisation. */
+int ragmi_depth_metrics_workspace_elems(long long n);
+int ragmi_depth_metrics_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10, int dtype,
+                            void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * clip_grad_norm_(max_norm) + torch.optim.SGD(lr, momentum, weight_decay).step() over flat fp32 buffers of n elements
  * (approaches/rag.py:64-70, 215-216) as two launches: g *= min(1, max_norm/(||g||+1e-6)) (max_norm <= 0: no clipping);

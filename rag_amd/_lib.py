@@ -135,6 +135,11 @@ SIGNATURES = {
     "ragmi_selfsup_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "ragmi_selfsup_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ragmi_depth_head_supported": (c_int, [c_int] * 7),
+    "ragmi_depth_head_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_float, c_int, c_void_p]),
+    "ragmi_depth_metrics_workspace_elems": (c_int, [ctypes.c_longlong]),
+    "ragmi_depth_metrics_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "ragmi_disp_softargmin_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_disp_softargmin_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p]),

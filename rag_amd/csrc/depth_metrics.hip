@@ -1,0 +1,117 @@
+// Loss + evaluation metrics of the monocular-depth eval loop (rag_depth/src/approaches/rag.py:440-489) as ONE pass over
+// (depth_est, depth_gt): the masked pixels gt > 0 of the whole batch, as the reference gathers them.  silog_loss
+// (utilstool/experiment.py:154-161) and compute_errors (approaches/rag.py:19-41) share their sums: with d = log est - log gt,
+//   n, sum d, sum d^2, sum |gt - est| / gt, sum (gt - est)^2 / gt, sum (gt - est)^2, sum |log10 est - log10 gt|,
+//   and the counts of max(gt/est, est/gt) < 1.25, 1.25^2, 1.25^3
+// (log_rms's (log gt - log est)^2 is d^2, bit for bit).  Per-pixel terms are fp32 like the reference's arrays; the sums are double.
+// Partials are reduced in a fixed order (an LDS tree per workgroup, then a one-workgroup finalize): no atomics, no memset, so the
+// result is bitwise reproducible and the call graph-capturable.  The reference does a boolean gather, a D2H copy and numpy per batch.
+#include "common.h"
+
+namespace ragmi {
+
+constexpr int DM_WG = 256;       // threads per workgroup, main pass and finalize
+constexpr int DM_NSUM = 10;      // sums per slot (order above)
+constexpr int DM_MAXWG = 1024;   // workgroups of the main pass at most (grid-stride beyond)
+
+__global__ __launch_bounds__(DM_WG) void depth_metrics_kernel(const float* __restrict__ est, const float* __restrict__ gt, int64_t n,
+                                                              double* __restrict__ slots) {
+  double v[DM_NSUM];
+#pragma unroll
+  for (int k = 0; k < DM_NSUM; ++k) v[k] = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * DM_WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * DM_WG) {
+    const float g = gt[i];
+    if (!(g > 0.f)) continue;
+    const float e = est[i];
+    const float d = logf(e) - logf(g);
+    const float diff = g - e;
+    const float sq = diff * diff;
+    const float th = fmaxf(g / e, e / g);
+    v[0] += 1.0;
+    v[1] += d;
+    v[2] += (double)(d * d);
+    v[3] += fabsf(diff) / g;
+    v[4] += sq / g;
+    v[5] += sq;
+    v[6] += fabsf(log10f(e) - log10f(g));
+    v[7] += th < 1.25f ? 1.0 : 0.0;
+    v[8] += th < 1.5625f ? 1.0 : 0.0;
+    v[9] += th < 1.953125f ? 1.0 : 0.0;
+  }
+  __shared__ double red[DM_NSUM][DM_WG];
+#pragma unroll
+  for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int s = DM_WG / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+#pragma unroll
+      for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < DM_NSUM) slots[(int64_t)blockIdx.x * DM_NSUM + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// out = silog_loss, then compute_errors: silog, abs_rel, log10, rms, sq_rel, log_rms, d1, d2, d3
+__global__ __launch_bounds__(DM_WG) void depth_metrics_finalize_kernel(const double* __restrict__ slots, int nslots, double variance_focus,
+                                                                       float* __restrict__ out) {
+  double v[DM_NSUM];
+#pragma unroll
+  for (int k = 0; k < DM_NSUM; ++k) v[k] = 0.0;
+  for (int s = threadIdx.x; s < nslots; s += DM_WG) {
+#pragma unroll
+    for (int k = 0; k < DM_NSUM; ++k) v[k] += slots[(int64_t)s * DM_NSUM + k];
+  }
+  __shared__ double red[DM_NSUM][DM_WG];
+#pragma unroll
+  for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int s = DM_WG / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+#pragma unroll
+      for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double n = red[0][0];                       // 0 masked pixels: every mean is 0/0 = NaN, as numpy's mean of an empty array
+    const double md = red[1][0] / n, md2 = red[2][0] / n;
+    out[0] = (float)(sqrt(md2 - variance_focus * md * md) * 10.0);
+    out[1] = (float)(sqrt(md2 - md * md) * 100.0);
+    out[2] = (float)(red[3][0] / n);
+    out[3] = (float)(red[6][0] / n);
+    out[4] = (float)sqrt(red[5][0] / n);
+    out[5] = (float)(red[4][0] / n);
+    out[6] = (float)sqrt(md2);
+    out[7] = (float)(red[7][0] / n);
+    out[8] = (float)(red[8][0] / n);
+    out[9] = (float)(red[9][0] / n);
+  }
+}
+
+static int depth_metrics_slots(long long n) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 4 * DM_WG), DM_MAXWG)); }
+
+}  // namespace ragmi
+
+extern "C" int ragmi_depth_metrics_workspace_elems(long long n) {
+  if (n <= 0) return 0;
+  return ragmi::depth_metrics_slots(n) * ragmi::DM_NSUM * 2;        // one double (two floats) per partial
+}
+
+extern "C" int ragmi_depth_metrics_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10,
+                                       int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(est && gt && workspace && out10, RAGMI_EINVAL, "depth_metrics: null pointer");
+  RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "depth_metrics: dtype %d not built (float32 only)", dtype);
+  RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "depth_metrics: bad size %lld", n);
+  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "depth_metrics: workspace not 8-byte aligned");
+  const int nslots = depth_metrics_slots(n);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(depth_metrics_kernel, dim3((unsigned)nslots), dim3(DM_WG), 0, st, (const float*)est, (const float*)gt, (int64_t)n,
+                     (double*)workspace);
+  hipLaunchKernelGGL(depth_metrics_finalize_kernel, dim3(1), dim3(DM_WG), 0, st, (const double*)workspace, nslots, (double)variance_focus,
+                     (float*)out10);
+  return check_launch("depth_metrics");
+}

@@ -1,0 +1,339 @@
+"""`Network` — the reference's grown monocular-depth model (rag_depth/src/models/rag_model.py:201-800) on the HIP kernels of
+``rag_amd``, for inference.
+
+The depth network is the stereo `rag_amd.network.Network` without the cost volume and the right image: the Matching-Net
+layers keep their names (``stem3d0``, ``cells_3d``, ``last_*_3d``, hence the checkpoint's state_dict keys) but are the 2-D
+modules (`ConvBR_2d`, `Cell_2d` built from ``genotype.normal``) over the left image's features, and `DispHead` + x3 bilinear +
+x ``max_depth`` replaces `Disp`.  The unit bookkeeping and the growth API (``expand`` / ``select`` / ``get_new_model`` /
+``get_param`` / ``modify_param``) are the stereo network's; only `_new_unit` differs.
+
+``forward(left, right, t, task_arch, path)`` runs the Feature Net and the 2-D matching chain on the existing kernels, the
+``last_12_3d`` -> ``upsample_12`` -> ``last_6_3d`` chain on the 1x1 kernels, and ``upsample_6`` -> ``last_3_3d`` -> DispHead ->
+x3 upsample -> x max_depth as ONE launch (``ops.depth_head``).  Training is out of scope: a call that would need autograd or
+batch statistics raises.
+
+`load_depth_checkpoint` rebuilds a grown model from the reference's ``checkpoint_task{t}.ckpt``; `depth_metrics` is the eval
+loop's silog_loss + compute_errors (approaches/rag.py:440-489) in one fused pass.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from .checkpoint import _HEADS, _check_cell_pattern, _genotype, _unit_counts
+from .modules import _CELL3D_ARCH, _ConvBR, ALL_CONV_ROWS, Cell_2d, ConvBR_2d, Genotype, _volume
+from .network import Network as _StereoNetwork
+
+MAX_DEPTH = 80          # rag_model.py:298
+DEPTH_NAMES = ("silog_loss", "silog", "abs_rel", "log10", "rms", "sq_rel", "log_rms", "d1", "d2", "d3")
+
+
+class DispHead(nn.Module):
+    """rag_model.py:51-64: sigmoid(conv1(x)) then x `scale` bilinear (align_corners=False).  `conv1` is Conv2d(input_dim, 1, 3,
+    padding=1) WITH bias.  Inside `Network.forward` the head is fused with upsample_6 and last_3_3d (ops.depth_head); called on its
+    own (input_dim 1) it is the same kernel with an identity 3x3 in place of last_3_3d."""
+
+    def __init__(self, input_dim=100):
+        super().__init__()
+        self.conv1 = nn.Conv2d(input_dim, 1, 3, padding=1)
+        self.sigmoid = nn.Sigmoid()              # kept for attribute parity; the sigmoid runs in the kernel
+
+    def forward(self, x, scale):
+        if x.dim() != 4 or x.shape[1] != 1 or self.conv1.in_channels != 1:
+            raise NotImplementedError("rag_amd DispHead: built for the one-channel head the depth network uses")
+        _refuse_autograd(x, self.conv1.weight, self.conv1.bias)
+        eye = _identity3x3(x.device)
+        return ops.depth_head(x, eye, self.conv1.weight.detach(), self.conv1.bias.detach(), x.shape[2:], int(scale), 1.0)[:, None]
+
+
+_EYE: Dict[str, torch.Tensor] = {}
+
+
+def _identity3x3(device) -> torch.Tensor:
+    key = str(device)
+    if key not in _EYE:
+        eye = torch.zeros((1, 1, 3, 3), dtype=torch.float32)
+        eye[0, 0, 1, 1] = 1.0
+        _EYE[key] = eye.to(device)
+    return _EYE[key]
+
+
+def _refuse_autograd(*ts) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError("rag_amd.depth: inference only (training the depth network is not built); "
+                           "call it under torch.no_grad() with the model in eval()")
+
+
+class Network(_StereoNetwork):
+    """rag_depth/src/models/rag_model.py:201-800.  Same constructor, attributes, ModuleList names and state_dict keys as the
+    reference; `depth_head` (never grown) and `max_depth = 80` in place of the stereo head."""
+
+    def __init__(self, genotype, device):
+        super().__init__(genotype, device, maxdisp=192)
+        self.depth_head = DispHead(input_dim=1)
+        self.max_depth = MAX_DEPTH
+
+    def _init_matching(self, genotype, maxdisp):
+        # rag_model.py:250-298: the stereo Matching-Net layers with their 2-D twins (same attribute names)
+        self._step = 3
+        self._block_multiplier = 3
+        self._filter_multiplier = 4
+        self._num_layers_3d = 8
+        for name in ("stem_3d0", "stem_3d1", "last_3_3d", "last_6_3d", "last_12_3d"):
+            self.length[name] = 1
+            self.arch_init[name] = [0]
+        self.cells_3d = nn.ModuleList()
+        self.stem3d0 = nn.ModuleList([self._new_unit("stem_3d0", genotype)])
+        self.stem3d1 = nn.ModuleList([self._new_unit("stem_3d1", genotype)])
+        for i in range(self._num_layers_3d):
+            self.cells_3d.append(nn.ModuleList([self._new_unit(f"cell_3d{i}", genotype)]))
+            self.arch_init[f"cell_3d{i}"] = [0]
+            self.length[f"cell_3d{i}"] = 1
+        self.last_3_3d = nn.ModuleList([self._new_unit("last_3_3d", genotype)])
+        self.last_6_3d = nn.ModuleList([self._new_unit("last_6_3d", genotype)])
+        self.last_12_3d = nn.ModuleList([self._new_unit("last_12_3d", genotype)])
+        self.maxdisp = maxdisp
+        from .modules import Disp
+        self.disp = Disp(self.maxdisp)          # the reference builds it too (unused, no parameters)
+
+    def _new_unit(self, name: str, genotype) -> nn.Module:
+        fm = 12
+        if name in ("stem_3d0", "stem_3d1"):
+            return ConvBR_2d(fm, fm, 3, stride=1, padding=1)
+        if name.startswith("cell_3d"):
+            pp, p, f, du = _CELL3D_ARCH[int(name[7:])]
+            return Cell_2d(3, 3, pp, p, genotype, f, du)
+        if name == "last_3_3d":
+            return ConvBR_2d(fm, 1, 3, 1, 1, bn=False, relu=False)
+        if name == "last_6_3d":
+            return ConvBR_2d(fm * 2, fm, 1, 1, 0)
+        if name == "last_12_3d":
+            return ConvBR_2d(fm * 4, fm * 2, 1, 1, 0)
+        return super()._new_unit(name, genotype)
+
+    # ------------------------------------------------------------------ inference paths
+    def _check_inference(self, x) -> None:
+        if self._training_graph(x):
+            raise RuntimeError("rag_amd.depth.Network: inference only (training the depth network is not built); call it under "
+                               "torch.no_grad() with the model in eval()")
+        if self.act_dtype != torch.float32 or x.dtype != torch.float32:
+            raise RuntimeError("rag_amd.depth.Network: fp32 only (bf16 activation storage is not built for the depth network)")
+
+    def _trunk(self, x, stem0, stem1, cells, m6, m12) -> torch.Tensor:
+        """stem3d0 -> stem3d1 -> cells (rag_model.py:363-373), then the head's 1x1 part: the input of upsample_6, at (h/2, w/2) or
+        already at (h, w) (rag_model.py:378-385)."""
+        out = (stem0(x),)
+        out = (out[0], stem1(out[0]))
+        for c in cells:
+            out = c(out[0], out[1])
+        last = out[-1]
+        h, w = x.shape[2], x.shape[3]
+        if last.shape[2] == h:
+            return last
+        if last.shape[2] == h // 2:
+            return m6(last)
+        if last.shape[2] != h // 4:
+            raise ValueError("rag_amd.depth.Network: feature height must be a multiple of 4 (input H a multiple of 12)")
+        half = (1, h // 2, w // 2)
+        last5 = last.unsqueeze(2)
+        if (m12._geometry() == 1 and m6._geometry() == 1 and ops.chain_k1_enabled() and _volume(half) > _volume(last5.shape[2:])
+                and m6.conv.out_channels <= m6.conv.in_channels
+                and ops.conv3d_k1_chain_supported(m12.conv.in_channels, m12.conv.out_channels, m6.conv.out_channels)):
+            # last_12_3d and last_6_3d's channel mix as ONE launch on the small volume, then the upsample_12 + ReLU (as the stereo head)
+            w1, s1, h1 = m12.prepared()
+            w2, s2, h2 = m6.prepared()
+            B = last.shape[0]
+            low = torch.empty((B, m6.conv.out_channels) + tuple(last5.shape[2:]), device=last.device, dtype=last.dtype)
+            ops.conv3d_k1_chain(last5, w1, s1, h1, m12.relu, w2, s2, h2, False, low)
+            y = torch.empty((B, m6.conv.out_channels) + half, device=last.device, dtype=last.dtype)
+            ops.trilinear3d_act(low, half, True, m6.relu, y, 0)
+            return y[:, :, 0]
+        return m6(m12(last), resample_to=half)
+
+    def _head(self, y6, size, m3) -> torch.Tensor:
+        if m3.use_bn or m3.relu or m3._geometry() != 3 or m3.conv.out_channels != 1:
+            raise NotImplementedError("rag_amd.depth.Network: last_3_3d must be the reference's 3x3 conv without BN / ReLU")
+        dh = self.depth_head.conv1
+        return ops.depth_head(y6, m3.conv.weight.detach(), dh.weight.detach(), dh.bias.detach(), size, 3, float(self.max_depth))
+
+    def _matching_units(self, task_arch, path):
+        def unit(name):
+            return task_arch[name][0] if task_arch is not None else None
+
+        cells = []
+        for i, cell in enumerate(self.cells_3d):
+            arch_cell = None
+            if task_arch is not None:
+                arch_cell = task_arch[f"cell_3d{i}"][0]
+            elif path is not None:
+                arch_cell = path[i + 1]
+            cells.append(cell[arch_cell])
+        return (self.stem3d0[unit("stem_3d0")], self.stem3d1[unit("stem_3d1")], cells, self.last_3_3d[unit("last_3_3d")],
+                self.last_6_3d[unit("last_6_3d")], self.last_12_3d[unit("last_12_3d")])
+
+    def matching(self, x, task_arch, path=None):                # rag_model.py:347-389 -> mat [B, 1, h, w]
+        self._check_inference(x)
+        stem0, stem1, cells, m3, m6, m12 = self._matching_units(task_arch, path)
+        y6 = self._trunk(x, stem0, stem1, cells, m6, m12)
+        h, w = x.shape[2], x.shape[3]
+        u = ops.trilinear3d(y6.unsqueeze(2), (1, h, w), True)
+        # last_3_3d on the VALU 3x3x3 form: the 2-D weight is the dz = 1 plane of a 3x3x3 over a depth-1 volume
+        key = (m3.stamp(),)
+        hit = getattr(m3, "_w5_cache", None)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                wt = m3.conv.weight.detach()
+                w5 = torch.zeros(wt.shape[:2] + (3, 3, 3), device=wt.device, dtype=wt.dtype)
+                w5[:, :, 1] = wt
+            hit = (key, w5)
+            m3._w5_cache = hit
+        mat = torch.empty((x.shape[0], 1, 1, h, w), device=x.device, dtype=torch.float32)
+        ops.conv3d_k3_small(u, hit[1], None, None, False, mat, 0)
+        return mat[:, :, 0]
+
+    def forward(self, left, right=None, t=None, task_arch=None, path=None):   # rag_model.py:391-416 (`right` is ignored)
+        self._check_inference(left)
+        x = self.feature(left, task_arch, path)
+        stem0, stem1, cells, m3, m6, m12 = self._matching_units(task_arch, path)
+        return self._head(self._trunk(x, stem0, stem1, cells, m6, m12), x.shape[2:], m3)
+
+    def search_forward(self, left, right, t, selected_ops):        # rag_model.py:716-740
+        self._check_inference(left)
+        x = self.search_feature(left, selected_ops)
+        cells = [cell[selected_ops[i + 10]] for i, cell in enumerate(self.cells_3d)]
+        y6 = self._trunk(x, self.stem3d0[selected_ops[8]], self.stem3d1[selected_ops[9]], cells, self.last_6_3d[t], self.last_12_3d[t])
+        return self._head(y6, x.shape[2:], self.last_3_3d[t])
+
+
+DepthNetwork = Network
+
+
+# ---------------------------------------------------------------------------------------------------------------- checkpoints
+def rows_from_keys(keys, prefix: str) -> np.ndarray:
+    """STAND-IN genotype rows of one cell unit from its state_dict keys: [[0,p0],[1,p1],[2,p2],[3,p3],[5,p4],[6,p5]] with pj = 1 when
+    positional op j has a convolution.  The reference never recorded the searched branches (upstream writes them to tensorboard
+    text only), so these rows reproduce the checkpoint's op TYPES, not necessarily its branch wiring."""
+    keys = set(keys)
+    branches = ALL_CONV_ROWS[:, 0]
+    return np.array([[int(br), int(f"{prefix}_ops.{j}.conv.weight" in keys)] for j, br in enumerate(branches)])
+
+
+def genotypes_from_keys(keys) -> Dict[str, List[np.ndarray]]:
+    """{layer: [stand-in rows per unit]} for every cell layer of a depth state_dict (see `rows_from_keys`)."""
+    counts = _unit_counts(keys)
+    out = {}
+    for name, n in counts.items():
+        if name.startswith("cell_"):
+            attr = "cells_2d" if name.startswith("cell_2d") else "cells_3d"
+            out[name] = [rows_from_keys(keys, f"{attr}.{name[7:]}.{idx}.") for idx in range(n)]
+    return out
+
+
+def _geno(g) -> Genotype:
+    if isinstance(g, (np.ndarray, list, tuple)) and not hasattr(g, "normal"):
+        rows = np.asarray(g)
+        return Genotype(normal=rows, normal_concat=None, reduce=rows, reduce_concat=None)
+    return _genotype(g)
+
+
+def load_depth_checkpoint(src: Union[str, dict], device="cuda", genotypes: Union[None, str, dict] = None,
+                          archis: Optional[Sequence[dict]] = None):
+    """-> (depth Network in eval mode on `device`, archis) from the reference's ``{'task', 'model', 'optimizer'}`` file
+    (rag_depth/src/run.py) or a dict holding ``model``.  The file is read with ``weights_only=True`` and the state_dict loaded strictly.
+
+    The reference checkpoint records no genotypes.  `genotypes`: ``{layer: [rows or Genotype per unit]}`` for every cell layer, or
+    ``"from_keys"`` for the stand-in rows of `rows_from_keys` (they reproduce each unit's conv / identity op types from the key
+    names, NOT necessarily the searched branch wiring, which upstream never saved).  Every cell is checked against its keys (ValueError
+    on a mismatch).  `archis`: per-task architecture dicts; None gives ``[net.arch_init]``."""
+    data = torch.load(src, map_location="cpu", weights_only=True) if not isinstance(src, dict) else src
+    sd = data["model"] if "model" in data else data
+    keys = set(sd.keys())
+    counts = _unit_counts(keys)
+    if genotypes is None:
+        raise ValueError("load_depth_checkpoint: the reference checkpoint records no genotypes; pass genotypes= (rows per unit, or "
+                         "'from_keys')")
+    if isinstance(genotypes, str):
+        if genotypes != "from_keys":
+            raise ValueError(f"load_depth_checkpoint: genotypes must be a dict or 'from_keys', got {genotypes!r}")
+        genotypes = genotypes_from_keys(keys)
+
+    def geno(name: str, idx: int) -> Genotype:
+        return _geno(genotypes[name][idx]) if isinstance(genotypes, dict) else _geno(genotypes)
+
+    first = geno("cell_3d0", 0)
+    net = Network(first, "cpu")
+    for name in net._p_layers() + list(_HEADS):
+        units = net._units(name)
+        want = counts.get(name, 1)
+        if name.startswith("cell_"):
+            units[0] = net._new_unit(name, geno(name, 0))
+        for idx in range(1, want):
+            units.append(net._new_unit(name, geno(name, idx) if name.startswith("cell_") else first))
+        if name not in _HEADS:
+            net.length[name] = want
+    for name in net._p_layers():
+        if name.startswith("cell_"):
+            attr = "cells_2d" if name.startswith("cell_2d") else "cells_3d"
+            for idx, unit in enumerate(net._units(name)):
+                _check_cell_pattern(unit, f"{attr}.{name[7:]}.{idx}.", keys, name, idx)
+    net.load_state_dict(sd, strict=True)
+    out_archis = list(archis) if archis is not None else [net.arch_init]
+    for t, a in enumerate(out_archis):
+        for name, (k, *_rest) in a.items():
+            if int(k) >= len(net._units(name)):
+                raise ValueError(f"load_depth_checkpoint: archis[{t}][{name!r}] = {k} but the checkpoint has "
+                                 f"{len(net._units(name))} unit(s)")
+    return net.to(device).eval(), [dict(a) for a in out_archis]
+
+
+# ---------------------------------------------------------------------------------------------------------------- metrics
+class DepthMetrics:
+    """Result of `depth_metrics`: `.tensor` is the 10-float device vector (DEPTH_NAMES order); `[name]` gives a 0-d device tensor;
+    `floats()` copies once to the host."""
+
+    def __init__(self, tensor: torch.Tensor):
+        self.tensor = tensor
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        return self.tensor[DEPTH_NAMES.index(name)]
+
+    def floats(self) -> Dict[str, float]:
+        return dict(zip(DEPTH_NAMES, self.tensor.tolist()))      # the only synchronisation
+
+
+def depth_metrics(depth_est: torch.Tensor, depth_gt: torch.Tensor, variance_focus: float = 0.85) -> DepthMetrics:
+    """silog_loss + compute_errors of the depth eval loop (approaches/rag.py:440-489) over the pixels with gt > 0 of the whole batch,
+    on the device, without the boolean gather or the per-batch D2H copy; no gradient."""
+    with torch.no_grad():
+        return DepthMetrics(ops.depth_metrics(depth_est.detach(), depth_gt.detach(), variance_focus))
+
+
+# ---------------------------------------------------------------------------------------------------------------- plain-torch twins
+def depth_head_torch(y, w3, w1, b1, size: Sequence[int], scale: int = 3, max_depth: float = 80.0) -> torch.Tensor:
+    """Plain-torch restatement of ops.depth_head in the dtype and on the device of its inputs (CPU twin and ATen yardstick)."""
+    import torch.nn.functional as F
+    u = F.interpolate(y, size=tuple(int(v) for v in size), mode="bilinear", align_corners=True)
+    m = F.conv2d(u, w3, padding=1)
+    s = torch.sigmoid(F.conv2d(m, w1, b1, padding=1))
+    if scale > 1:
+        s = F.interpolate(s, scale_factor=scale, mode="bilinear", align_corners=False)
+    return s[:, 0] * max_depth
+
+
+def depth_metrics_torch(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85) -> torch.Tensor:
+    """Plain-torch restatement of ops.depth_metrics: per-pixel terms in the inputs' dtype, means in float64."""
+    mask = gt > 0
+    e, g = est[mask], gt[mask]
+    d = torch.log(e) - torch.log(g)
+    diff = g - e
+    th = torch.maximum(g / e, e / g)
+    mean = lambda t: t.double().mean()  # noqa: E731
+    md, md2 = mean(d), mean(d * d)
+    out = [torch.sqrt(md2 - variance_focus * md * md) * 10.0, torch.sqrt(md2 - md * md) * 100.0, mean(diff.abs() / g),
+           mean((torch.log10(e) - torch.log10(g)).abs()), torch.sqrt(mean(diff * diff)), mean(diff * diff / g), torch.sqrt(md2),
+           mean((th < 1.25).to(e.dtype)), mean((th < 1.25 ** 2).to(e.dtype)), mean((th < 1.25 ** 3).to(e.dtype))]
+    return torch.stack(out)

@@ -1017,3 +1017,49 @@ def sgd_clip_step(param: torch.Tensor, grad: torch.Tensor, buf: torch.Tensor, lr
                                   float(weight_decay), float(max_norm), int(first_step), workspace.data_ptr(), norm_out.data_ptr(),
                                   _stream()), "sgd_clip_step")
     return norm_out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# monocular-depth network (rag_depth): fused head and loss + metrics
+def depth_head_supported(cin: int, hi: int, wi: int, h: int, w: int, scale: int = 3, dtype=torch.float32) -> bool:
+    return bool(load_library().ragmi_depth_head_supported(cin, hi, wi, h, w, scale, _DT.get(dtype, -1)))
+
+
+def depth_head(y: torch.Tensor, w3: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, size: Sequence[int], scale: int = 3,
+               max_depth: float = 80.0) -> torch.Tensor:
+    """upsample_6 -> last_3_3d -> DispHead(., scale) -> x max_depth as ONE launch: y [B, Cin, Hi, Wi] (last_6_3d's output) ->
+    depth [B, scale*H, scale*W] with (H, W) = size.  w3: last_3_3d's [1, Cin, 3, 3] weight, w1 / b1: DispHead.conv1's [1, 1, 3, 3]
+    weight and [1] bias (read on the device).  fp32 only: any other dtype is refused by the library."""
+    for t in (y, w3, w1, b1):
+        if not t.is_cuda:
+            raise RuntimeError("rag_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
+    if y.dim() != 4 or w3.numel() != 9 * y.shape[1] or w1.numel() != 9 or b1.numel() != 1:
+        raise ValueError("depth_head: y must be [B, Cin, Hi, Wi], w3 [1, Cin, 3, 3], w1 [1, 1, 3, 3], b1 [1]")
+    dtypes = {y.dtype, w3.dtype, w1.dtype, b1.dtype}
+    dt = _DT.get(y.dtype, -1) if len(dtypes) == 1 else -1      # the library refuses what it was not built for
+    y, w3, w1, b1 = y.contiguous(), w3.contiguous(), w1.contiguous(), b1.contiguous()
+    B, C, Hi, Wi = y.shape
+    H, W = (int(v) for v in size)
+    out = torch.empty((B, scale * H, scale * W), device=y.device, dtype=torch.float32)
+    check(load_library().ragmi_depth_head_fwd(y.data_ptr(), w3.data_ptr(), w1.data_ptr(), b1.data_ptr(), out.data_ptr(), B, C, Hi, Wi,
+                                              H, W, int(scale), float(max_depth), dt, _stream()), "depth_head")
+    return out
+
+
+def depth_metrics(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85) -> torch.Tensor:
+    """[silog_loss, silog, abs_rel, log10, rms, sq_rel, log_rms, d1, d2, d3] over the pixels with gt > 0 of the whole batch, as a
+    10-float device tensor (two launches, no sync)."""
+    for t in (est, gt):
+        if not t.is_cuda:
+            raise RuntimeError("rag_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
+    if est.shape != gt.shape or est.numel() == 0:
+        raise ValueError("depth_metrics: est and gt must have the same non-empty shape")
+    dt = _DT.get(est.dtype, -1) if est.dtype == gt.dtype else -1
+    est, gt = est.contiguous(), gt.contiguous()
+    lib = load_library()
+    n = est.numel()
+    ws = torch.empty((max(2, lib.ragmi_depth_metrics_workspace_elems(n)),), device=est.device, dtype=torch.float32)
+    out = torch.empty((10,), device=est.device, dtype=torch.float32)
+    check(lib.ragmi_depth_metrics_fwd(est.data_ptr(), gt.data_ptr(), n, float(variance_focus), ws.data_ptr(), out.data_ptr(), dt,
+                                      _stream()), "depth_metrics")
+    return out
