@@ -589,6 +589,36 @@ int ragmi_depth_metrics_workspace_elems(long long n);
 int ragmi_depth_metrics_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10, int dtype,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Backward of ragmi_depth_head_fwd (the depth training step, rag_depth/src/approaches/rag.py:182-246; the forward chain is
+ * rag_model.py:51-64, 357-416): d_out [B, scale*H, scale*W] -> dy [B, Cin, Hi, Wi] (written), dw3 [Cin*9], dw1 [9], db1 [1]
+ * (accumulate: bit 0 for dw3, bit 1 for dw1, bit 2 for db1; a clear bit writes the gradient, a set bit adds it to what the buffer
+ * holds, e.g. a gradient bucket's view).  u, m, z and s are recomputed from y;
+ * the forward saves nothing.  Same shapes and dtype as the forward (ragmi_depth_head_supported); all pointers non-NULL; workspace:
+ * ragmi_depth_head_bwd_workspace_elems(B, Cin, H, W) floats, 8-byte aligned, scratch.  Two launches, no atomics (bitwise
+ * reproducible), no memset, no host synchronisation. */
+int64_t ragmi_depth_head_bwd_workspace_elems(int B, int Cin, int H, int W);
+int ragmi_depth_head_bwd(const void* y, const void* w3, const void* w1, const void* b1, const void* d_out, void* dy, void* dw3,
+                         void* dw1, void* db1, int accumulate, void* workspace, int B, int Cin, int Hi, int Wi, int H, int W, int scale,
+                         float max_depth, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * silog_loss of the depth training step (rag_depth/src/utilstool/experiment.py:154-161, used at approaches/rag.py:237-239) over
+ * the n pixels of (est, gt) with gt > 0, the whole batch together: d = log est - log gt,
+ *   out[0] = 10 sqrt(mean d^2 - variance_focus mean(d)^2)      (float)
+ *   saved  = {n, mean d, sqrt(mean d^2 - variance_focus mean(d)^2)}   (3 doubles, 8-byte aligned; input of the backward)
+ * No masked pixel gives the reference's NaN loss.  workspace: ragmi_silog_loss_workspace_elems(n) floats, 8-byte aligned, scratch.
+ * fp32 only (dtype must be RAGMI_F32; bf16 is refused with RAGMI_EUNSUPPORTED).  Two launches, no atomics (bitwise reproducible),
+ * no memset, no host synchronisation. */
+int ragmi_silog_loss_workspace_elems(long long n);
+int ragmi_silog_loss_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out, void* saved,
+                         int dtype, void* stream);
+
+/* gradient of out[0]: grad[i] = gout[0] * 10 (d_i - variance_focus mean d) / (n sqrt(.) est_i) where gt > 0, else 0; all zeros
+ * when n = 0 (the loss is then NaN, but no NaN reaches a gradient).  gout is read on the device.  One launch. */
+int ragmi_silog_loss_bwd(const void* est, const void* gt, long long n, float variance_focus, const void* saved, const void* gout,
+                         void* grad, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * clip_grad_norm_(max_norm) + torch.optim.SGD(lr, momentum, weight_decay).step() over flat fp32 buffers of n elements
  * (approaches/rag.py:64-70, 215-216) as two launches: g *= min(1, max_norm/(||g||+1e-6)) (max_norm <= 0: no clipping);

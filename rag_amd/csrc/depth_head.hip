@@ -7,14 +7,9 @@
 // One workgroup owns a DH_TH x DH_TW tile of s.  It stages u over tile+3 (all channels) in LDS, builds m over tile+2 and s over
 // tile+1 in LDS, then writes its 3*DH_TH output rows with 16-byte stores along W.  The 12-channel full-resolution u and the
 // one-channel m and s never reach HBM.  fp32 storage and arithmetic.  DESIGN.md section 4.6.
-#include "common.h"
+#include "depth_common.h"
 
 namespace ragmi {
-
-constexpr int DH_TH = 8, DH_TW = 32, DH_THREADS = 256, DH_CMAX = 16;
-constexpr int DH_UH = DH_TH + 6, DH_UW = DH_TW + 6;   // u: tile + 3 on every side
-constexpr int DH_MH = DH_TH + 4, DH_MW = DH_TW + 4;   // m: tile + 2
-constexpr int DH_SH = DH_TH + 2, DH_SW = DH_TW + 2;   // s: tile + 1
 
 struct DepthHeadArgs {
   const float* y;     // [B, Cin, Hi, Wi]
@@ -28,21 +23,6 @@ struct DepthHeadArgs {
   float max_depth;
   int vec;            // the output rows can take 16-byte stores (S*W % 4 == 0 and `out` 16-byte aligned)
 };
-
-// ATen's linear source index, weights and neighbour for one axis (upsample_bilinear2d)
-__device__ __forceinline__ void src_ac(int dst, float scale, int in, int& i0, int& i1, float& l1) {
-  const float r = scale * (float)dst;                 // align_corners=True
-  i0 = (int)r;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = r - (float)i0;
-}
-__device__ __forceinline__ void src_half(int dst, float inv_s, int in, int& i0, int& i1, float& l1) {
-  float r = inv_s * ((float)dst + 0.5f) - 0.5f;       // align_corners=False, clamped at 0
-  r = r < 0.f ? 0.f : r;
-  i0 = (int)r;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = r - (float)i0;
-}
 
 __global__ __launch_bounds__(DH_THREADS) void depth_head_kernel(const DepthHeadArgs a) {
   __shared__ float su[DH_CMAX][DH_UH * DH_UW];

@@ -1,5 +1,5 @@
 """`Network` — the reference's grown monocular-depth model (rag_depth/src/models/rag_model.py:201-800) on the HIP kernels of
-``rag_amd``, for inference.
+``rag_amd``, for inference and training.
 
 The depth network is the stereo `rag_amd.network.Network` without the cost volume and the right image: the Matching-Net
 layers keep their names (``stem3d0``, ``cells_3d``, ``last_*_3d``, hence the checkpoint's state_dict keys) but are the 2-D
@@ -9,11 +9,16 @@ x ``max_depth`` replaces `Disp`.  The unit bookkeeping and the growth API (``exp
 
 ``forward(left, right, t, task_arch, path)`` runs the Feature Net and the 2-D matching chain on the existing kernels, the
 ``last_12_3d`` -> ``upsample_12`` -> ``last_6_3d`` chain on the 1x1 kernels, and ``upsample_6`` -> ``last_3_3d`` -> DispHead ->
-x3 upsample -> x max_depth as ONE launch (``ops.depth_head``).  Training is out of scope: a call that would need autograd or
-batch statistics raises.
+x3 upsample -> x max_depth as ONE launch (``ops.depth_head``).  It is inference only: a call that would need autograd or batch
+statistics raises and names the training entry point.
 
-`load_depth_checkpoint` rebuilds a grown model from the reference's ``checkpoint_task{t}.ckpt``; `depth_metrics` is the eval
-loop's silog_loss + compute_errors (approaches/rag.py:440-489) in one fused pass.
+``forward_train(left, t, task_arch, path)`` is the training forward of Appr.train_epoch (approaches/rag.py:182-246): the trunk on
+the `rag_amd.autograd` Functions (train-mode BatchNorm where a unit is in train()), the head through `DepthHeadFn` (the same fused
+forward launch; its backward is ``ops.depth_head_bwd``).  `silog_loss` is the loss of that step (utilstool/experiment.py:154-161)
+with its fused HIP gradient; ``rag_amd.train`` drives both.  `search_forward` and a standalone `DispHead` stay inference only.
+
+`load_depth_checkpoint` rebuilds a grown model from the reference's ``checkpoint_task{t}.ckpt`` (``train()`` it to fine-tune or grow
+a task); `depth_metrics` is the eval loop's silog_loss + compute_errors (approaches/rag.py:440-489) in one fused pass.
 """
 from __future__ import annotations
 
@@ -64,8 +69,65 @@ def _identity3x3(device) -> torch.Tensor:
 
 def _refuse_autograd(*ts) -> None:
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
-        raise RuntimeError("rag_amd.depth: inference only (training the depth network is not built); "
-                           "call it under torch.no_grad() with the model in eval()")
+        raise RuntimeError("rag_amd.depth: inference only (a standalone DispHead has no backward; the depth network trains through "
+                           "Network.forward_train); call it under torch.no_grad() with the model in eval()")
+
+
+class DepthHeadFn(torch.autograd.Function):
+    """upsample_6 -> last_3_3d -> DispHead(., scale) -> x max_depth (rag_model.py:51-64, 357-416): the fused forward launch, and
+    ops.depth_head_bwd (two launches, u / m / s recomputed from y) as its backward.  Weight gradients go straight into bucket-backed
+    .grad views (rag_amd.autograd._direct) when there are some."""
+
+    @staticmethod
+    def forward(ctx, y, w3, w1, b1, size, scale, max_depth):
+        size = tuple(int(v) for v in size)
+        ctx.size, ctx.scale, ctx.max_depth = size, int(scale), float(max_depth)
+        ctx.params = (w3, w1, b1)
+        ctx.save_for_backward(y, w3, w1, b1)
+        return ops.depth_head(y.detach(), w3.detach(), w1.detach(), b1.detach(), size, ctx.scale, ctx.max_depth)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        from .autograd import _direct
+        y, w3, w1, b1 = ctx.saved_tensors
+        need = ctx.needs_input_grad[1:4]
+        direct = [_direct(p) if n else None for p, n in zip(ctx.params, need)]
+        dy, dw3, dw1, db1 = ops.depth_head_bwd(y, w3.detach(), w1.detach(), b1.detach(), d_out, ctx.size, ctx.scale, ctx.max_depth,
+                                               *direct)
+        grads = [None if (not n or t is not None) else g for g, n, t in zip((dw3, dw1, db1), need, direct)]
+        return (dy if ctx.needs_input_grad[0] else None, *grads, None, None, None)
+
+
+class SilogLossFn(torch.autograd.Function):
+    """silog_loss (utilstool/experiment.py:154-161) over gt > 0: two launches forward, one backward (ops.silog_loss / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, est, gt, variance_focus):
+        out, saved = ops.silog_loss(est.detach(), gt.detach(), variance_focus)
+        ctx.vf = float(variance_focus)
+        ctx.save_for_backward(est, gt, saved)
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, grad):
+        est, gt, saved = ctx.saved_tensors
+        return ops.silog_loss_bwd(est.detach(), gt, saved, grad, ctx.vf), None, None
+
+
+def silog_loss(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85) -> torch.Tensor:
+    """The depth training loss (utilstool/experiment.py:154-161, mask gt > 0): 10 sqrt(mean d^2 - variance_focus mean(d)^2),
+    d = log est - log gt, as a 0-d tensor with a gradient w.r.t. `est`.  On the GPU the fused HIP loss (no boolean gather, no
+    synchronisation); on the CPU `silog_loss_torch`.  No pixel with gt > 0: NaN loss (as the reference) and an all-zero gradient."""
+    if est.is_cuda:
+        return SilogLossFn.apply(est, gt, float(variance_focus))
+    return silog_loss_torch(est, gt, variance_focus)
+
+
+def silog_loss_torch(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85) -> torch.Tensor:
+    """Plain-torch restatement of the reference's silog_loss (CPU twin of `silog_loss`; the boolean gather synchronises)."""
+    mask = gt > 0
+    d = torch.log(est[mask]) - torch.log(gt[mask])
+    return torch.sqrt((d ** 2).mean() - variance_focus * (d.mean() ** 2)) * 10.0
 
 
 class Network(_StereoNetwork):
@@ -118,14 +180,15 @@ class Network(_StereoNetwork):
     # ------------------------------------------------------------------ inference paths
     def _check_inference(self, x) -> None:
         if self._training_graph(x):
-            raise RuntimeError("rag_amd.depth.Network: inference only (training the depth network is not built); call it under "
-                               "torch.no_grad() with the model in eval()")
+            raise RuntimeError("rag_amd.depth.Network: forward is inference only; call it under torch.no_grad() with the model in "
+                               "eval(), or train through Network.forward_train (rag_amd.train.train_step drives it)")
         if self.act_dtype != torch.float32 or x.dtype != torch.float32:
             raise RuntimeError("rag_amd.depth.Network: fp32 only (bf16 activation storage is not built for the depth network)")
 
-    def _trunk(self, x, stem0, stem1, cells, m6, m12) -> torch.Tensor:
+    def _trunk(self, x, stem0, stem1, cells, m6, m12, train: bool = False) -> torch.Tensor:
         """stem3d0 -> stem3d1 -> cells (rag_model.py:363-373), then the head's 1x1 part: the input of upsample_6, at (h/2, w/2) or
-        already at (h, w) (rag_model.py:378-385)."""
+        already at (h, w) (rag_model.py:378-385).  `train`: the unfused m6(m12(.), resample_to=half) chain, whose units have
+        autograd forms (the one-launch 1x1 chain is inference only)."""
         out = (stem0(x),)
         out = (out[0], stem1(out[0]))
         for c in cells:
@@ -140,7 +203,7 @@ class Network(_StereoNetwork):
             raise ValueError("rag_amd.depth.Network: feature height must be a multiple of 4 (input H a multiple of 12)")
         half = (1, h // 2, w // 2)
         last5 = last.unsqueeze(2)
-        if (m12._geometry() == 1 and m6._geometry() == 1 and ops.chain_k1_enabled() and _volume(half) > _volume(last5.shape[2:])
+        if (not train and m12._geometry() == 1 and m6._geometry() == 1 and ops.chain_k1_enabled() and _volume(half) > _volume(last5.shape[2:])
                 and m6.conv.out_channels <= m6.conv.in_channels
                 and ops.conv3d_k1_chain_supported(m12.conv.in_channels, m12.conv.out_channels, m6.conv.out_channels)):
             # last_12_3d and last_6_3d's channel mix as ONE launch on the small volume, then the upsample_12 + ReLU (as the stereo head)
@@ -200,6 +263,20 @@ class Network(_StereoNetwork):
         x = self.feature(left, task_arch, path)
         stem0, stem1, cells, m3, m6, m12 = self._matching_units(task_arch, path)
         return self._head(self._trunk(x, stem0, stem1, cells, m6, m12), x.shape[2:], m3)
+
+    def forward_train(self, left, t=None, task_arch=None, path=None):   # rag_model.py:391-416 under autograd (approaches/rag.py:234)
+        """The training forward: -> depth [B, 3h, 3w] with an autograd graph through the HIP Functions of rag_amd.autograd and
+        `DepthHeadFn`.  BatchNorm uses batch statistics in the units that are in train() and running statistics in the others, as
+        the reference's train_epoch (reused units in eval()).  fp32 only."""
+        if self.act_dtype != torch.float32 or left.dtype != torch.float32:
+            raise RuntimeError("rag_amd.depth.Network: training is fp32 only")
+        x = self.feature(left, task_arch, path)
+        stem0, stem1, cells, m3, m6, m12 = self._matching_units(task_arch, path)
+        y6 = self._trunk(x, stem0, stem1, cells, m6, m12, train=True)
+        if m3.use_bn or m3.relu or m3._geometry() != 3 or m3.conv.out_channels != 1:
+            raise NotImplementedError("rag_amd.depth.Network: last_3_3d must be the reference's 3x3 conv without BN / ReLU")
+        dh = self.depth_head.conv1
+        return DepthHeadFn.apply(y6, m3.conv.weight, dh.weight, dh.bias, x.shape[2:], 3, float(self.max_depth))
 
     def search_forward(self, left, right, t, selected_ops):        # rag_model.py:716-740
         self._check_inference(left)

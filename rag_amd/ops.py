@@ -1063,3 +1063,69 @@ def depth_metrics(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0
     check(lib.ragmi_depth_metrics_fwd(est.data_ptr(), gt.data_ptr(), n, float(variance_focus), ws.data_ptr(), out.data_ptr(), dt,
                                       _stream()), "depth_metrics")
     return out
+
+
+def depth_head_bwd(y: torch.Tensor, w3: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, d_out: torch.Tensor, size: Sequence[int],
+                   scale: int = 3, max_depth: float = 80.0, dw3_into: Optional[torch.Tensor] = None,
+                   dw1_into: Optional[torch.Tensor] = None, db1_into: Optional[torch.Tensor] = None):
+    """Backward of `depth_head` (two launches): -> (dy, dw3, dw1, db1).  A weight gradient given `*_into` (a contiguous fp32 tensor of
+    the weight's size, e.g. a GradBucket view) is ADDED to it and returned as that tensor; otherwise it is a fresh tensor shaped like
+    the weight."""
+    _need_gpu(y, w3, w1, b1, d_out)
+    if y.dim() != 4 or w3.numel() != 9 * y.shape[1] or w1.numel() != 9 or b1.numel() != 1:
+        raise ValueError("depth_head_bwd: y must be [B, Cin, Hi, Wi], w3 [1, Cin, 3, 3], w1 [1, 1, 3, 3], b1 [1]")
+    B, C, Hi, Wi = y.shape
+    H, W = (int(v) for v in size)
+    if tuple(d_out.shape) != (B, scale * H, scale * W):
+        raise ValueError(f"depth_head_bwd: d_out must be [{B}, {scale * H}, {scale * W}], got {tuple(d_out.shape)}")
+    dtypes = {y.dtype, w3.dtype, w1.dtype, b1.dtype, d_out.dtype}
+    dt = _DT.get(y.dtype, -1) if len(dtypes) == 1 else -1
+    y, w3, w1, b1, d_out = y.contiguous(), w3.contiguous(), w1.contiguous(), b1.contiguous(), d_out.contiguous()
+    outs, acc = [], 0
+    for bit, (w, into) in enumerate(((w3, dw3_into), (w1, dw1_into), (b1, db1_into))):
+        if into is not None:
+            if into.numel() != w.numel() or into.dtype != torch.float32 or not into.is_contiguous() or into.device != w.device:
+                raise ValueError("depth_head_bwd: an *_into target must be a contiguous fp32 tensor of the weight's size")
+            outs.append(into)
+            acc |= 1 << bit
+        else:
+            outs.append(torch.empty(w.shape, device=w.device, dtype=torch.float32))
+    dy = torch.empty((B, C, Hi, Wi), device=y.device, dtype=torch.float32)
+    lib = load_library()
+    ws = torch.empty((max(2, lib.ragmi_depth_head_bwd_workspace_elems(B, C, H, W)),), device=y.device, dtype=torch.float32)
+    check(lib.ragmi_depth_head_bwd(y.data_ptr(), w3.data_ptr(), w1.data_ptr(), b1.data_ptr(), d_out.data_ptr(), dy.data_ptr(),
+                                   outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), acc, ws.data_ptr(), B, C, Hi, Wi, H, W,
+                                   int(scale), float(max_depth), dt, _stream()), "depth_head_bwd")
+    return dy, outs[0], outs[1], outs[2]
+
+
+def silog_loss(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85):
+    """silog_loss over the pixels with gt > 0 of the whole batch (two launches, no sync) -> (loss [1], saved: float64 [3] =
+    n, mean d, sqrt(mean d^2 - variance_focus mean(d)^2), the input of `silog_loss_bwd`)."""
+    for t in (est, gt):
+        if not t.is_cuda:
+            raise RuntimeError("rag_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
+    if est.shape != gt.shape or est.numel() == 0:
+        raise ValueError("silog_loss: est and gt must have the same non-empty shape")
+    dt = _DT.get(est.dtype, -1) if est.dtype == gt.dtype else -1
+    est, gt = est.contiguous(), gt.contiguous()
+    lib = load_library()
+    n = est.numel()
+    ws = torch.empty((max(2, lib.ragmi_silog_loss_workspace_elems(n)),), device=est.device, dtype=torch.float32)
+    out = torch.empty((1,), device=est.device, dtype=torch.float32)
+    saved = torch.empty((3,), device=est.device, dtype=torch.float64)
+    check(lib.ragmi_silog_loss_fwd(est.data_ptr(), gt.data_ptr(), n, float(variance_focus), ws.data_ptr(), out.data_ptr(),
+                                   saved.data_ptr(), dt, _stream()), "silog_loss")
+    return out, saved
+
+
+def silog_loss_bwd(est: torch.Tensor, gt: torch.Tensor, saved: torch.Tensor, gout: torch.Tensor, variance_focus: float = 0.85):
+    """d silog_loss / d est, scaled by the device scalar `gout` (one launch); zero where gt <= 0, and everywhere when no pixel has
+    gt > 0."""
+    _need_gpu(gout)
+    dt = _DT.get(est.dtype, -1) if est.dtype == gt.dtype else -1
+    est, gt, gout = est.contiguous(), gt.contiguous(), gout.reshape(-1)[:1].contiguous()
+    grad = torch.empty(est.shape, device=est.device, dtype=torch.float32)
+    check(load_library().ragmi_silog_loss_bwd(est.data_ptr(), gt.data_ptr(), est.numel(), float(variance_focus), saved.data_ptr(),
+                                              gout.data_ptr(), grad.data_ptr(), dt, _stream()), "silog_loss_bwd")
+    return grad

@@ -81,7 +81,19 @@ def self_supervised_loss(disp: torch.Tensor, left: torch.Tensor, right: torch.Te
     return re_and_sm_loss_torch(disp, left, right)[0]
 
 
-def _check_supervision(gt, features: bool, supervise: bool) -> None:
+def _is_depth(net) -> bool:
+    from .depth import Network as DepthNetwork
+    return isinstance(net, DepthNetwork)
+
+
+def _check_supervision(gt, features: bool, supervise: bool, depth: bool = False) -> None:
+    if depth:
+        if not supervise or features:
+            raise ValueError("a depth network trains on silog_loss(depth, gt) from the left image only: supervise=False and "
+                             "features=True are refused")
+        if gt is None:
+            raise ValueError("the depth training step needs the ground-truth depth gt (metres, 0 = invalid)")
+        return
     if not supervise and features:
         raise ValueError("supervise=False needs the images (the loss warps the right image onto the left): features=True is refused")
     if supervise and gt is None:
@@ -93,17 +105,24 @@ TRAIN_PRECISION = "fp32"     # the reference's training step is fp32 (rag.py:204
 
 def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None, features: bool = False,
                      precision: Optional[str] = None, supervise: bool = True):
-    """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  `supervise=False`: the self-supervised loss
+    """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  A depth network (rag_amd.depth.Network):
+    Network.forward_train(left) -> silog_loss(depth, gt) with gt the ground-truth depth in metres (0 = invalid) as in
+    rag_depth/src/approaches/rag.py:232-242; `right` may be None.  `supervise=False`: the self-supervised loss
     re_and_sm_loss(disp, left, right) of src_self (approaches/rag.py:270-278) instead, `gt` may be None, and left/right must be
     the images (features=True raises ValueError).  `features=True`: `net` is a
     MatchingNet and left/right are Feature-Net outputs.  `precision`: arithmetic of the 3x3x3 convolutions of the step (forward and
     data gradient): "fp32" (default, TRAIN_PRECISION: every contraction on the fp32-input MFMA forms, the reference's arithmetic
     class) or "f16x3" (opt-in; bound in include/rag_amd.h).  Returns the (detached) loss."""
-    _check_supervision(gt, features, supervise)
+    depth = _is_depth(net)
+    _check_supervision(gt, features, supervise, depth)
     from . import ops
     with ops.conv_precision(precision or TRAIN_PRECISION):
-        disp = net(left, right, task_arch) if features else net(left, right, 0, task_arch if task_arch is not None else net.arch_init)
-        loss = masked_smooth_l1(disp, gt, net.maxdisp) if supervise else self_supervised_loss(disp, left, right)
+        if depth:
+            from .depth import silog_loss
+            loss = silog_loss(net.forward_train(left, 0, task_arch if task_arch is not None else net.arch_init), gt)
+        else:
+            disp = net(left, right, task_arch) if features else net(left, right, 0, task_arch if task_arch is not None else net.arch_init)
+            loss = masked_smooth_l1(disp, gt, net.maxdisp) if supervise else self_supervised_loss(disp, left, right)
         bucket.zero()
         loss.backward()
     return loss.detach()
@@ -201,13 +220,15 @@ class GraphedTrainStep:
     is not established, so the invariant is ENFORCED rather than assumed: the captured graph's nodes are counted at capture time
     (ragmi_graph_node_census) and a capture holding any memcpy / memset node is refused — an ATen op that starts lowering to
     copy_ or memset after a torch upgrade fails loudly here instead of corrupting a replay.  The graph replays on the caller's
-    current stream; no private stream is involved.  `supervise=False`: the self-supervised step of src_self (gt may be None)."""
+    current stream; no private stream is involved.  `supervise=False`: the self-supervised step of src_self (gt may be None).
+    A depth network: the silog step of forward_backward (right may be None)."""
 
     def __init__(self, net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                  features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True):
-        _check_supervision(gt, features, supervise)
+        _check_supervision(gt, features, supervise, _is_depth(net))
         self.net, self.opt, self.bucket, self.clip, self.dist = net, optimizer, bucket, clip, dist
-        self.left, self.right = left.clone(), right.clone()
+        self.left = left.clone()
+        self.right = right.clone() if right is not None else None
         self.gt = gt.clone() if gt is not None else None
         self.precision = precision or TRAIN_PRECISION
         kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise)
