@@ -18,6 +18,7 @@ Two execution modes, both on the HIP kernels, neither with a PyTorch fallback:
 from __future__ import annotations
 
 from collections import namedtuple
+from types import MappingProxyType
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -413,7 +414,7 @@ class _Cell(nn.Module):
         return any(m.use_bn and m.bn.training for m in units)
 
     def forward(self, prev_prev_input, prev_input):
-        run = self._run_autograd if self.autograd_mode(prev_prev_input, prev_input) else (lambda a, b: self._run(a, b)[0])
+        run = self._run_autograd if self.autograd_mode(prev_prev_input, prev_input) else self._run
         if prev_input.dim() == 4:     # 2-D cell: run on depth-1 volumes
             return prev_input, run(prev_prev_input.unsqueeze(2), prev_input.unsqueeze(2)).squeeze(2)
         return prev_input, run(prev_prev_input, prev_input)
@@ -467,72 +468,59 @@ class _Cell(nn.Module):
             return tuple(int(v) for v in prev_size)
         return tuple(self.scale_dimension(int(v), self.scale) for v in prev_size)
 
-    def dual_plan(self, s0_channels: int, s0_from_tail: bool = True) -> bool:
-        """True when ONE dual launch produces every new state of this cell (what `_run` calls single_dual): both inputs feed conv
-        branches into all of them and nothing else does — a property of the genotype (and of whether s0 goes through pre_preprocess)."""
-        C = self.C_out
+    def dual_branches(self, s0_in_pre: bool):
+        """(a, b, whole): the conv branches leaving s0 and s1 as [(new state k, op)] when they run as ONE dual launch — both feed
+        the same new states, nothing else feeds those, and they share a buffer — else (None, None, False); `whole`: that launch produces
+        every new state of the cell, so consumer tails can ride on it.  A property of the genotype and of whether s0 sits in the
+        cell's s0|s1 buffer (it went through pre_preprocess, here or as its producer's tail)."""
         contribs = self._contributions()
-        conv_from = {j: [(k, op) for k, lst in contribs.items() for (src, op) in lst if src == j and isinstance(op, _ConvBR)] for j in (0, 1)}
-        return (bool(conv_from[0]) and (s0_from_tail or s0_channels != C) and [k for k, _ in conv_from[0]] == [k for k, _ in conv_from[1]]
-                and all(len(contribs[k]) == 2 for k, _ in conv_from[0]) and len(conv_from[0]) == self._steps
-                and self.block_multiplier == self._steps)
+        a, b = ([(k, op) for k, lst in contribs.items() for (src, op) in lst if src == j and isinstance(op, _ConvBR)] for j in (0, 1))
+        first_cat = 2 + self._steps - self.block_multiplier
+        if not (a and s0_in_pre and [k for k, _ in a] == [k for k, _ in b] and all(len(contribs[k]) == 2 for k, _ in a)
+                and len({k >= first_cat for k, _ in a}) == 1):
+            return None, None, False
+        return a, b, len(a) == self._steps and self.block_multiplier == self._steps
 
-    def _run(self, prev_prev_input, prev_input, pre: Optional[torch.Tensor] = None, pre_has=(False, False),
-             tails: Optional[Sequence["ops.Tail"]] = None, store_main: bool = True, size: Optional[Sequence[int]] = None,
-             pre_g4: bool = False, dtype: Optional[torch.dtype] = None):
-        """forward() plus the cross-cell fusion hooks used by MatchingNet.matching (`dtype`: this cell's storage type when it is not
-        its inputs' — mixed storage, MatchingNet._run_chain):
-        `pre`/`pre_has`: the [B, 2C, ...] buffer in which the producers of the inputs have already written s0 (ch 0..C)
-        and/or s1 (ch C..2C) as fused tails; `tails`/`store_main`: consumer 1x1x1 convs to compute in THIS cell's final
-        conv launch (possible when one dual launch produces all new states).  Returns (concat or None, tails_applied)."""
+    def _run(self, prev_prev_input, prev_input, plan: Optional["_CellPlan"] = None, pre: Optional[torch.Tensor] = None,
+             tails: Optional[Sequence["ops.Tail"]] = None):
+        """forward() plus the cross-cell fusion of MatchingNet._run_chain: `plan` is this cell's slice of the chain plan (None: a
+        stand-alone cell — nothing arrives fused, everything is stored), `pre` the [B, 2C, ...] buffer in which s0 (ch 0..C) and /
+        or s1 (ch C..2C) have already been written as `plan.has` says, `tails` the consumer 1x1x1 convs the plan put on THIS
+        cell's dual launch (`plan.tails`).  Returns the concat, or None when the plan does not store it."""
         C = self.C_out
         if C % 4 != 0 or self.block_multiplier > self._steps:
             raise NotImplementedError("rag_amd.Cell_3d: filter_multiplier must be a multiple of 4 and "
                                       "block_multiplier <= steps (true for every cell the reference builds)")
         s0, s1 = prev_prev_input, prev_input
+        pre_has = plan.has if plan is not None else (False, False)
+        a, b, whole = self.dual_branches(pre_has[0] or s0.shape[1] != C)
+        if plan is None:
+            plan = _CellPlan(size=self.out_size(s1.shape[2:]), dtype=s1.dtype, has=pre_has, g4=False, dual=whole, store_main=True, tails=False,
+                             shared_pre=False)
         # the trilinear resamples (rag_model.py:146-153) are fused into the 1x1x1 preprocess convs that consume them
-        if size is None:
-            size = self.out_size(s1.shape[2:])
-        size = tuple(int(v) for v in size)
+        size = tuple(int(v) for v in plan.size)
         if not pre_has[0] and s0.shape[1] == C and tuple(s0.shape[2:]) != size:
             s0 = ops.trilinear3d(s0, size, True)     # no pre_preprocess to fuse into (never the case in Network)
         D, H, W = size
-        if (D == 1 and pre is None and not tails and store_main and s0.shape[1] != C and s1.dtype == torch.float32 and s0.dtype == torch.float32
-                and ops.get_conv_precision() == "f16x3" and self.block_multiplier == self._steps):
+        if (D == 1 and whole and pre is None and not tails and plan.store_main and s0.shape[1] != C and s1.dtype == torch.float32
+                and s0.dtype == torch.float32 and ops.get_conv_precision() == "f16x3"
+                and ops.cell2d_supported(C, s0.shape[1], s1.shape[1], C * self._steps, H, W)):
             # A Cell_2d in which every new state is conv(s0) + conv(s1) (the all-conv genotype): ONE launch — the two 1x1 ConvBRs and
             # their bilinear resamples run in the staging of the dual 3x3 launch (ragmi_cell2d_fwd); s0 / s1 are never written
-            contribs = self._contributions()
-            from_ = {j: [(k, op) for k, lst in contribs.items() for (src, op) in lst if src == j and isinstance(op, _ConvBR)] for j in (0, 1)}
-            if (len(from_[0]) == self._steps and [k for k, _ in from_[0]] == [k for k, _ in from_[1]]
-                    and all(len(contribs[k]) == 2 for k, _ in from_[0])
-                    and ops.cell2d_supported(C, s0.shape[1], s1.shape[1], C * self._steps, H, W)):
-                cat = torch.empty((s1.shape[0], self.block_multiplier * C, D, H, W), device=s1.device, dtype=s1.dtype)
-                pa, sa, ha = self._fused([op for _k, op in from_[0]])
-                pb, sb, hb = self._fused([op for _k, op in from_[1]])
-                first = 2 + self._steps - self.block_multiplier
-                groups = [(k - first) * C + 4 * g for k, _op in from_[0] for g in range(C // 4)]
-                ops.cell2d(s0, self.pre_preprocess.prepared() + (self.pre_preprocess.relu,), s1,
-                           self.preprocess.prepared() + (self.preprocess.relu,), C, pa, sa, ha, pb, sb, hb, C * self._steps, True, cat, groups)
-                return cat, False
-        if pre_g4 and not (pre is not None and pre_has[0] and pre_has[1]):
-            raise RuntimeError("rag_amd.Cell_3d: a G4 input buffer must arrive complete from its producers' fused tails")
+            cat = torch.empty((s1.shape[0], self.block_multiplier * C, D, H, W), device=s1.device, dtype=s1.dtype)
+            pa, sa, ha = self._fused([op for _k, op in a])
+            pb, sb, hb = self._fused([op for _k, op in b])
+            groups = [(k - 2) * C + 4 * g for k, _op in a for g in range(C // 4)]
+            ops.cell2d(s0, self.pre_preprocess.prepared() + (self.pre_preprocess.relu,), s1,
+                       self.preprocess.prepared() + (self.preprocess.relu,), C, pa, sa, ha, pb, sb, hb, C * self._steps, True, cat, groups)
+            return cat
         if pre is None:
-            B, dev = s1.shape[0], s1.device
-            pre = torch.empty((B, 2 * C, D, H, W), device=dev, dtype=dtype or s1.dtype)
+            pre = torch.empty((s1.shape[0], 2 * C, D, H, W), device=s1.device, dtype=plan.dtype)
         B, dev, adt = pre.shape[0], pre.device, pre.dtype
         n_states = 2 + self._steps
         first_cat = n_states - self.block_multiplier             # first state that lands in the concat buffer
-        tails_applied = False
         contribs = self._contributions()
-        conv_from = {j: [(k, op) for k, lst in contribs.items() for (src, op) in lst
-                         if src == j and isinstance(op, _ConvBR)] for j in (0, 1)}
-        # one dual launch produces every new state <=> both inputs feed conv branches into all of them and nothing else does
-        single_dual = (bool(conv_from[0]) and (pre_has[0] or s0.shape[1] != C) and [k for k, _ in conv_from[0]] == [k for k, _ in conv_from[1]]
-                       and all(len(contribs[k]) == 2 for k, _ in conv_from[0]) and len(conv_from[0]) == self._steps
-                       and self.block_multiplier == self._steps)
-        use_tails = bool(tails) and single_dual and C * self._steps <= 16
-        drop_main = use_tails and not store_main
-        cat = (pre if drop_main else   # placeholder pointer: nothing is stored when the output is only consumed by tails
+        cat = (pre if not plan.store_main else   # placeholder pointer: nothing is stored when the output is only consumed by tails
                torch.empty((B, self.block_multiplier * C, D, H, W), device=dev, dtype=adt))
         scratch = (torch.empty((B, (first_cat - 2) * C, D, H, W), device=dev, dtype=adt)
                    if first_cat > 2 else None)
@@ -591,22 +579,16 @@ class _Cell(nn.Module):
         # (e.g. the all-conv genotype): ONE dual-input launch computes relu(bn(conv(s0))) + relu(bn(conv(s1)))
         # for all of them, so the running sum never goes through HBM.
         done = set()
-        if (conv_from[0] and where[0][0] is pre and [k for k, _ in conv_from[0]] == [k for k, _ in conv_from[1]]
-                and all(len(contribs[k]) == 2 and not pending_id[k] for k, _ in conv_from[0])
-                and len({id(where[k][0]) for k, _ in conv_from[0]}) == 1):
-            pa, sa, ha = self._fused([op for _k, op in conv_from[0]])
-            pb, sb, hb = self._fused([op for _k, op in conv_from[1]])
-            groups = [where[k][1] + 4 * g for k, _op in conv_from[0] for g in range(C // 4)]
-            ops.conv3d_k3_dual(pre, C, pa, sa, ha, pb, sb, hb, C * len(conv_from[0]), True,
-                               where[conv_from[0][0][0]][0], groups,
-                               tails=tails if use_tails else None, store_main=not drop_main, x_g4=pre_g4)
-            tails_applied = use_tails
-            for j in (0, 1):
-                for k, op in conv_from[j]:
+        if a is not None:
+            pa, sa, ha = self._fused([op for _k, op in a])
+            pb, sb, hb = self._fused([op for _k, op in b])
+            groups = [where[k][1] + 4 * g for k, _op in a for g in range(C // 4)]
+            ops.conv3d_k3_dual(pre, C, pa, sa, ha, pb, sb, hb, C * len(a), True, where[a[0][0]][0], groups,
+                               tails=tails, store_main=plan.store_main, x_g4=plan.g4)
+            for j, branches in enumerate((a, b)):
+                for k, op in branches:
                     written[k] = True
                     done.add((j, id(op)))
-        elif pre_g4:
-            raise RuntimeError("rag_amd.Cell_3d: a G4 input buffer was planned for a cell that does not run as one dual launch")
 
         for j in range(n_states):
             if j >= 2:
@@ -657,9 +639,7 @@ class _Cell(nn.Module):
                                       res_buf, rg if res_buf is not None else None)
         for k in contribs:
             finalize(k)
-        if tails_applied and drop_main:
-            return None, True          # the concat exists only inside the kernel: its consumers were the tails
-        return cat, tails_applied
+        return cat if plan.store_main else None      # (not stored: the concat existed only inside the kernel, for its tails)
 
 
 class Cell_3d(_Cell):
@@ -682,6 +662,130 @@ class Cell_2d(_Cell):
 # (prev_prev_fmultiplier, prev_filter_multiplier, filter_multiplier, downup_sample)
 _CELL3D_ARCH = ((4, 4, 4, 0), (4, 4, 4, 0), (4, 4, 4, 0), (4, 4, 8, -1),
                 (4, 8, 16, -1), (8, 16, 8, 1), (16, 8, 16, -1), (8, 16, 16, 0))
+
+
+# What the fused executor (MatchingNet._run_chain) does at one shape, as data.  Tensors: T[-2] = stem3d0's output, T[-1] = stem3d1's,
+# T[i] = cell i's; cell i reads T[i-2] (prev_prev, role 0) and T[i-1] (prev, role 1).
+#   _CellPlan: size / dtype of the cell's s0|s1 buffer and of its output; has = which halves of that buffer are written before the cell
+#   runs (fused tails, shared_pre); g4 = the buffer is channel-group-interleaved; dual = one dual launch produces every new state
+#   (_Cell.dual_branches); store_main = the concat is written; tails = its consumers ride on that launch (else they run as plain 1x1x1
+#   launches behind it); shared_pre = its two 1x1x1 convs and cell i+1's pre_preprocess run as one launch in front of it.
+#   _ChainPlan: sizes[i], cdt[i] (storage type), consumers[i] = ((cell j, role, down), ...) fused onto T[i]'s producer, stored[i] for
+#   i = -2 .. n-1; cells = the _CellPlans; stem0_g4 = T[-2] is G4; stems_fused = both stems as one call (T[-2] never written);
+#   stem_tail_rows = cell 0's pre_preprocess in the idle rows of stem3d1's matrix product.
+_CellPlan = namedtuple("_CellPlan", "size dtype has g4 dual store_main tails shared_pre")
+_ChainPlan = namedtuple("_ChainPlan", "sizes cdt consumers stored cells stem0_g4 stems_fused stem_tail_rows")
+
+
+def _down_tail_ok(prod, cons, B, src, dst, src_dt, dst_dt) -> bool:
+    """cell `cons`' 1x1x1 conv on the output of cell `prod` as DOWN-SAMPLING tails of `prod`: `cons` works at exactly half of that size, the
+    source pairs of that x0.5 resampling are aligned, and the producer is a level-3 dual launch with 12 output channels on the z-marching
+    split-operand kernel (fp32 storage under the default precision, or bf16 storage) — the only form that takes them.  A bf16 producer
+    may write fp32 down-sampling tails (RAGMI_TAIL_F32); nothing else crosses storage types."""
+    return ((src_dt != torch.float32 or ops.get_conv_precision() == "f16x3")
+            and (dst_dt == src_dt or (src_dt == torch.bfloat16 and dst_dt == torch.float32))
+            and tuple(2 * v for v in dst) == tuple(src) and ops.down2_tail_supported(*src)
+            and cons.C_out <= 8 and cons.C_out % 4 == 0 and prod.downup_sample == 0 and prod.C_out == 4 and prod.C_out * prod._steps <= 16
+            and ops.conv3d_k3_uses_x3(2 * prod.C_out, prod.C_out * prod._steps, B, *src, nset=2, ntail=1, dtype=src_dt))
+
+
+def _plan_chain(stem0, stem1, cells, B: int, C_fea: int, vol, adt: torch.dtype, folded: bool) -> _ChainPlan:
+    """Every decision of the fused executor for stem3d0 -> stem3d1 -> cells (rag_model.py:341-351) on a [B, ., *vol] cost volume stored as
+    `adt` (`folded`: stem3d0 consumes the [B, C_fea, h, w] feature maps instead of the volume).  Reads module structure, the ops switches
+    and the library's host predicates; touches no tensor and launches nothing."""
+    n = len(cells)
+    f32, bf16 = torch.float32, torch.bfloat16
+    caps = ops.conv3d_k3_g4_caps
+    x3 = (adt == f32 and ops.get_conv_precision() == "f16x3") or adt == bf16      # the split-operand kernels: what G4 and the fused stems need
+    # Sizes, and the storage type per cell (mixed storage): under bf16 storage only the FULL-RESOLUTION tensors stay bf16 — a cell that
+    # works below the cost volume's resolution (at most 1/ratio of its voxels), and every cell behind one, keeps fp32
+    # (ops.set_bf16_deep_fp32: the level-12 cells and the head carry most of the bf16 error, the deep levels ~4 % of the bytes;
+    # tests/analysis_bf16_stage_epe.py).  The edges that cross are bf16 -> fp32 only: down-sampling tails (RAGMI_TAIL_F32) and the
+    # resample + 1x1x1 launch (RAGMI_OUT_F32).
+    sizes, cdt = {-2: tuple(vol), -1: tuple(vol)}, {-2: adt, -1: adt}
+    cout = {-2: stem0.conv.out_channels, -1: stem1.conv.out_channels}       # channels of T[i]
+    for i, c in enumerate(cells):
+        sizes[i] = c.out_size(sizes[i - 1])
+        deep = adt == bf16 and ops.bf16_deep_fp32_enabled() and (
+            _volume(sizes[i]) * ops.bf16_deep_fp32_ratio() <= _volume(vol) or f32 in (cdt[i - 1], cdt[i - 2]))
+        cdt[i] = f32 if deep else adt
+        cout[i] = c.block_multiplier * c.C_out
+
+    # Consumers of T[i] that can ride on its producer: a 4-channel 1x1x1 conv at the producer's size and storage type as a full-resolution
+    # tail, one a level down as down-sampling tails.  A prev_prev edge skips a module, which must keep the size (for cell 0 that is
+    # stem3d1), and exists only where the consumer has a pre_preprocess to run.
+    consumers = {}
+    for i in range(-2, n):
+        found = []
+        for j, role in ((i + 1, 1), (i + 2, 0)):
+            c = cells[j] if 0 <= j < n else None
+            if c is None or (role == 0 and (c.C_prev_prev == c.C_out or (j > 0 and cells[j - 1].downup_sample != 0))):
+                continue
+            if c.downup_sample == 0 and c.C_out == 4 and cdt[j] == cdt[i]:
+                found.append((j, role, False))
+            elif c.downup_sample == -1 and i >= 0 and _down_tail_ok(cells[i], c, B, sizes[i], sizes[j], cdt[i], cdt[j]):
+                found.append((j, role, True))
+        consumers[i] = tuple(found)
+    nfull = {i: sum(not d for (_j, _r, d) in consumers[i]) for i in consumers}                                  # tails of T[i]'s producer launch
+    ndown = {i: sum((cells[j].C_out + 3) // 4 for (j, _r, d) in consumers[i] if d) for i in consumers}
+    # one dual launch per cell (s0 sits in the s0|s1 buffer when it arrives as a tail or goes through pre_preprocess), which then takes tails
+    dual = [c.dual_branches((i, 0, False) in consumers[i - 2] or (i, 0, True) in consumers[i - 2] or cout[i - 2] != c.C_out)[2]
+            for i, c in enumerate(cells)]
+    tails = {i: bool(consumers[i]) and dual[i] and cout[i] <= 16 for i in range(n)}
+    tails[-2] = tails[-1] = True      # (the stems always apply theirs)
+
+    # G4: which of the private level-3 tensors are stored channel-group-interleaved ([B][C/4][D][H][W][4], include/rag_amd.h) instead of as
+    # channel planes.  Cell j's s0|s1 buffer can be G4 when cell j runs as ONE dual launch on the kernel that reads G4 (caps bit 0) and BOTH
+    # halves arrive as full-resolution tails from producers that can write G4 (bit 1; stem3d0 folded with the cost volume always can).
+    # The full-resolution tails of one producer launch share a layout, so candidates are withdrawn until every producer is consistent.
+    # T[-2] can be G4 when nothing but stem3d1 and fused tails reads it.  Everything else, and every module boundary, stays planes.
+    g4_ok = x3 and ops.g4_enabled()
+    writes = {i: bool(g4_ok and nfull[i] and tails[i]
+                      and caps(2 * c.C_out, cout[i], B, *sizes[i], nset=2, ntail=nfull[i], ndown=ndown[i], dtype=cdt[i]) & 2)
+              for i, c in enumerate(cells)}
+    writes[-2] = bool(g4_ok and nfull[-2] and (folded or caps(stem0.conv.in_channels, cout[-2], B, *vol, nset=1, ntail=nfull[-2], dtype=adt) & 2))
+    writes[-1] = bool(g4_ok and nfull[-1] and caps(cout[-2], cout[-1], B, *vol, nset=1, ntail=nfull[-1], dtype=adt) & 2)
+    g4 = [bool((j, 1, False) in consumers[j - 1] and (j, 0, False) in consumers[j - 2] and writes[j - 1] and writes[j - 2] and dual[j]
+               and caps(2 * c.C_out, cout[j], B, *sizes[j], nset=2, ntail=nfull[j] if tails[j] else 0, ndown=ndown[j] if tails[j] else 0,
+                        dtype=cdt[j]) & 1) for j, c in enumerate(cells)]
+    changed = True
+    while changed:          # one layout per producer launch
+        changed = False
+        for i in range(-2, n):
+            js = [j for (j, _r, d) in consumers[i] if not d]
+            if len({g4[j] for j in js}) > 1:
+                for j in js:
+                    g4[j] = False
+                changed = True
+    # stem3d0's own output is read by stem3d1 (3x3x3) and by cell 0's pre_preprocess tail only
+    alone = folded and (0, 0, False) in consumers[-2]
+    stem0_g4 = bool(g4_ok and alone and caps(cout[-2], cout[-1], B, *vol, nset=1, ntail=nfull[-1], dtype=adt) & 1)
+    stems_fused = bool(x3 and alone and ops.stem_fusion_enabled() and cout[-2] == 12 and stem1._geometry() == 3 and not stem1._small()
+                       and ops.costvol_stem_conv3d_supported(C_fea, 12, cout[-1], B, *vol, ntail=nfull[-1], dtype=adt))
+    # (that one tail has four output channels — a full-resolution consumer always has — so it fits rows 12..15 of a 12-channel stem3d1)
+    stem_tail_rows = stems_fused and ops.stem_tail_rows_enabled() and cout[-1] == 12
+
+    # a main output is stored unless every reader is a tail of its producer (the head reads the last one)
+    stored = {i: i == n - 1 or not tails[i] or len(consumers[i]) < sum(0 <= j < n for j in (i + 1, i + 2)) for i in range(-1, n)}
+    stored[-2] = not stems_fused
+    has = [[False, False] for _ in cells]
+    plans = []
+    for i in range(-2, n):
+        if i >= 0:
+            # shared_pre: cells i and i+1 both resample T[i-1] to the SAME size and nothing of either buffer is there yet — one launch for
+            # cell i's two 1x1x1 convs and cell i+1's pre_preprocess (not across storage types, and not for an up-sampling input, which
+            # runs conv-first with its cell)
+            j = i + 1
+            shared = (j < n and not any(has[i]) and not has[j][0] and sizes[i] == sizes[j] != sizes[i - 1] and stored[i - 2] and stored[i - 1]
+                      and cout[i - 2] != cells[i].C_out and cout[i - 1] != cells[j].C_out and len({cdt[i - 2], cdt[i - 1], cdt[i], cdt[j]}) == 1
+                      and _volume(sizes[i]) <= min(_volume(sizes[i - 2]), _volume(sizes[i - 1])))
+            if shared:
+                has[i], has[j][0] = [True, True], True
+            plans.append(_CellPlan(sizes[i], cdt[i], tuple(has[i]), g4[i], dual[i], stored[i], tails[i], shared))
+        for (j, role, _d) in consumers[i]:
+            has[j][role] = True
+    ro = MappingProxyType
+    return _ChainPlan(ro(sizes), ro(cdt), ro(consumers), ro(stored), tuple(plans), stem0_g4, stems_fused, stem_tail_rows)
 
 
 class MatchingNet(nn.Module):
@@ -760,7 +864,8 @@ class MatchingNet(nn.Module):
         """stem3d0 -> stem3d1 -> cells (rag_model.py:341-351) with cross-module fusion: the 1x1x1 pre_preprocess /
         preprocess conv of a cell that needs no resampling is computed in the epilogue of the kernel that PRODUCES its
         input (a "tail"), and a tensor consumed only by tails is never written to HBM.  Tensors: T[-2] = stem0 output,
-        T[-1] = stem1 output, T[i] = output of cell i; cell i reads T[i-2] (prev_prev) and T[i-1] (prev)."""
+        T[-1] = stem1 output, T[i] = output of cell i; cell i reads T[i-2] (prev_prev) and T[i-1] (prev).  Inference: `_plan_chain`
+        decides everything up front (per call: it reads the ops switches); the code below allocates and launches what the plan says."""
         train = (stem0.autograd_mode(*(features if x is None else (x,))) or stem1.autograd_mode()
                  or any(c.autograd_mode() for c in cells))
         if x is None and (train or not stem0.costvol_fusable(features[0].shape[1])):
@@ -772,225 +877,75 @@ class MatchingNet(nn.Module):
                 out = c(out[0], out[1])
             return out[-1]
         n = len(cells)
-        vol = self._vol_size(x, features)
-        sizes = {-2: vol, -1: vol}
-        for i, c in enumerate(cells):
-            sizes[i] = c.out_size(sizes[i - 1])
         ref = x if x is not None else features[0]
-        B, dev, adt = ref.shape[0], ref.device, ref.dtype
-        # Storage type per cell (round 5, mixed storage of BASELINE configs[2]): under bf16 storage only the FULL-RESOLUTION tensors stay
-        # bf16 — a cell that works below the cost volume's resolution (at most 1/8 of its voxels), and every cell behind one, keeps fp32
-        # (ops.set_bf16_deep_fp32: the level-12 cells and the head carry most of the bf16 error, the deep levels ~4 % of the bytes;
-        # tests/analysis_bf16_stage_epe.py).  cdt[j] = dtype of cell j's s0|s1 buffer
-        # and of its output; the stems' outputs keep `adt`.  The edges that cross are bf16 -> fp32 only: down-sampling tails
-        # (RAGMI_TAIL_F32) and the resample + 1x1x1 launch (RAGMI_OUT_F32).
-        cdt: Dict[int, torch.dtype] = {-2: adt, -1: adt}
-        for j in range(n):
-            deep = adt == torch.bfloat16 and ops.bf16_deep_fp32_enabled() and (
-                _volume(sizes[j]) * ops.bf16_deep_fp32_ratio() <= _volume(vol) or cdt[j - 1] == torch.float32 or cdt[j - 2] == torch.float32)
-            cdt[j] = torch.float32 if deep else adt
-
-        def down_ok(i, j):
-            """cell j's 1x1x1 conv on T[i] as DOWN-SAMPLING tails of T[i]'s producer: cell j works at exactly half of T[i]'s size,
-            the source pairs of that x0.5 resampling are aligned, and the producer is a level-3 dual launch on the z-marching
-            split-operand kernel (fp32 storage under the default precision, or bf16 storage) — the only form that takes them"""
-            if i < 0 or (cdt[i] == torch.float32 and ops.get_conv_precision() != "f16x3"):
-                return False
-            if cdt[j] != cdt[i] and not (cdt[i] == torch.bfloat16 and cdt[j] == torch.float32):
-                return False          # (a bf16 producer may write fp32 down-sampling tails: RAGMI_TAIL_F32; nothing else crosses)
-            src, dst, prod = sizes[i], sizes[j], cells[i]
-            if tuple(2 * v for v in dst) != tuple(src) or not ops.down2_tail_supported(*src):
-                return False
-            cj = cells[j]
-            if cj.C_out > 8 or cj.C_out % 4 != 0:
-                return False
-            # the producer: one dual launch with all its new states (what `_run` calls single_dual), 12 output channels, on the x3 form
-            if prod.downup_sample != 0 or prod.C_out * prod._steps > 16 or prod.C_out != 4:
-                return False
-            return ops.conv3d_k3_uses_x3(2 * prod.C_out, prod.C_out * prod._steps, B, *src, nset=2, ntail=1, dtype=cdt[i])
-
-        def fusable(i):
-            """consumers of T[i] that can ride on its producer: [(cell index j, role 0 = pre_preprocess / 1 = preprocess, down)]"""
-            out = []
-            j = i + 1
-            same = lambda jj: cdt[jj] == cdt[i]  # noqa: E731  (full-resolution tails store the producer's own type)
-            if 0 <= j < n and cells[j].downup_sample == 0 and cells[j].C_out <= 4 and cells[j].C_out % 4 == 0 and same(j):
-                out.append((j, 1, False))
-            elif 0 <= j < n and cells[j].downup_sample == -1 and down_ok(i, j):
-                out.append((j, 1, True))
-            j = i + 2
-            # (the cell between producer and consumer keeps the size: for j == 0 that "cell" is stem3d1 — same size by construction —
-            # not cells[-1], the LAST cell)
-            mid_same = j - 1 < 0 or (j - 1 < n and cells[j - 1].downup_sample == 0)
-            if (0 <= j < n and cells[j].downup_sample == 0 and mid_same and cells[j].C_out <= 4
-                    and cells[j].C_out % 4 == 0 and cells[j].C_prev_prev != cells[j].C_out and same(j)):
-                out.append((j, 0, False))
-            elif (0 <= j < n and cells[j].downup_sample == -1 and mid_same and cells[j].C_prev_prev != cells[j].C_out
-                  and down_ok(i, j)):
-                out.append((j, 0, True))
-            return out
-
-        def all_consumers(i):
-            return [(j, r) for (j, r) in ((i + 1, 1), (i + 2, 0)) if 0 <= j < n]
-
+        B, dev = ref.shape[0], ref.device
+        plan = _plan_chain(stem0, stem1, cells, B, ref.shape[1], self._vol_size(x, features), ref.dtype, x is None)
+        sizes, keep1 = plan.sizes, plan.stored[-1]
+        self.last_g4_plan = {"pre": {j: cp.g4 for j, cp in enumerate(plan.cells)}, "stem0_out": plan.stem0_g4,      # (tests and tools read it)
+                             "stems_fused": plan.stems_fused, **({"stem_tail_rows": plan.stem_tail_rows} if plan.stems_fused else {})}
         pre: Dict[int, torch.Tensor] = {}
-        has: Dict[int, List[bool]] = {}
 
-        # --- G4 plan (round 5): which of the private level-3 tensors are stored channel-group-interleaved ([B][C/4][D][H][W][4],
-        # include/rag_amd.h) instead of as channel planes.  pre[j] (cell j's s0|s1 buffer) can be G4 when cell j runs as ONE dual launch
-        # on the kernel that reads G4 (ops.conv3d_k3_g4_caps bit 0) and BOTH halves arrive as full-resolution fused tails from producers
-        # that can write G4 (bit 1; stem3d0 folded with the cost volume always can).  The full-resolution tails of one producer launch
-        # share a layout, so candidates are withdrawn until every producer is consistent.  T[-2] (stem3d0 -> stem3d1) can be G4 when
-        # nothing but stem3d1 and fused tails reads it.  Everything else, and every module boundary, stays channel planes.
-        def n_tails(i):
-            """(full-resolution, down-sampling) tail counts of T[i]'s producer launch"""
-            f = fusable(i)
-            return (sum(1 for (_j, _r, d) in f if not d), sum((cells[j].C_out + 3) // 4 for (j, _r, d) in f if d))
+        def buf(j):
+            """cell j's s0|s1 buffer"""
+            if j not in pre:
+                pre[j] = torch.empty((B, 2 * cells[j].C_out) + sizes[j], device=dev, dtype=plan.cdt[j])
+            return pre[j]
 
-        def out_channels(i):
-            return (stem0 if i == -2 else stem1).conv.out_channels if i < 0 else cells[i].block_multiplier * cells[i].C_out
+        def unit(j, role):
+            """(the 1x1x1 conv of cell j on its input `role` (0 prev_prev, 1 prev), cell j's s0|s1 buffer, the conv's first channel there)"""
+            return cells[j].preprocess if role else cells[j].pre_preprocess, buf(j), cells[j].C_out * role
 
-        def writes_g4(i):
-            """T[i]'s producer applies its fused tails and can write them G4"""
-            nt, nd = n_tails(i)
-            if i == -2:
-                return x is None or bool(ops.conv3d_k3_g4_caps(stem0.conv.in_channels, out_channels(-2), B, *vol, nset=1, ntail=nt, dtype=adt) & 2)
-            if i == -1:
-                return bool(ops.conv3d_k3_g4_caps(out_channels(-2), out_channels(-1), B, *vol, nset=1, ntail=nt, dtype=adt) & 2)
-            c = cells[i]
-            return (c.dual_plan(out_channels(i - 2)) and c.C_out * c._steps <= 16
-                    and bool(ops.conv3d_k3_g4_caps(2 * c.C_out, c.C_out * c._steps, B, *sizes[i], nset=2, ntail=nt, ndown=nd, dtype=cdt[i]) & 2))
+        def tails(i):
+            """the planned consumers of T[i] as tails of its producer"""
+            out = []
+            for (j, role, down) in plan.consumers[i]:
+                mod, dst, ch0 = unit(j, role)
+                out += mod.as_down_tails(dst, ch0) if down else [mod.as_tail(dst, ch0, g4=plan.cells[j].g4)]
+            return out or None
 
-        g4: Dict[int, bool] = {}
-        g4_ok = ((adt == torch.float32 and ops.get_conv_precision() == "f16x3") or adt == torch.bfloat16) and ops.g4_enabled()
-        for j in range(n):
-            c = cells[j]
-            nt, nd = n_tails(j)
-            g4[j] = (g4_ok and (j, 1, False) in fusable(j - 1) and (j, 0, False) in fusable(j - 2) and c.dual_plan(out_channels(j - 2))
-                     and bool(ops.conv3d_k3_g4_caps(2 * c.C_out, c.C_out * c._steps, B, *sizes[j], nset=2, ntail=nt if c.C_out * c._steps <= 16 else 0,
-                                                    ndown=nd if c.C_out * c._steps <= 16 else 0, dtype=cdt[j]) & 1)
-                     and writes_g4(j - 1) and writes_g4(j - 2))
-        changed = True
-        while changed:          # one layout per producer launch
-            changed = False
-            for i in range(-2, n):
-                js = [j for (j, _r, d) in fusable(i) if not d]
-                if len({g4[j] for j in js}) > 1:
-                    for j in js:
-                        g4[j] = False
-                    changed = True
-        # stem3d0's own output: read by stem3d1 (3x3x3) and by cell 0's fused pre_preprocess tail only
-        t2_g4 = (g4_ok and x is None and n >= 1 and (0, 0, False) in fusable(-2)
-                 and bool(ops.conv3d_k3_g4_caps(out_channels(-2), out_channels(-1), B, *vol, nset=1, ntail=n_tails(-1)[0], dtype=adt) & 1))
-
-        self.last_g4_plan = {"pre": dict(g4), "stem0_out": bool(t2_g4)}      # (what the tests and tools read)
-
-        def tails_for(i):
-            """[(consumer cell j, role, [Tail, ...])]: one full-resolution tail, or the one / two down-sampling tails of a consumer
-            that works one level down"""
-            specs = []
-            for (j, role, down) in fusable(i):
-                if j not in pre:
-                    pre[j] = torch.empty((B, 2 * cells[j].C_out) + sizes[j], device=dev, dtype=cdt[j])
-                    has[j] = [False, False]
-                mod = cells[j].preprocess if role == 1 else cells[j].pre_preprocess
-                ch0 = cells[j].C_out if role == 1 else 0
-                specs.append((j, role, mod.as_down_tails(pre[j], ch0) if down else [mod.as_tail(pre[j], ch0, g4=g4[j])]))
-            return specs
-
-        def flat(specs):
-            return [t for (_j, _r, ts) in specs for t in ts] or None
-
-        def settle(i, specs, applied, tensor):
-            """mark fused consumers as done, or run them as plain 1x1x1 launches if the producer could not fuse them"""
-            for (j, role, ts) in specs:
-                if not applied:
-                    if g4[j]:
-                        raise RuntimeError("rag_amd.MatchingNet: a producer planned to write a G4 tail did not apply its tails")
-                    mod = cells[j].preprocess if role == 1 else cells[j].pre_preprocess
-                    mod(tensor, out=pre[j], out_ch0=ts[0].out_ch0, resample_to=sizes[j] if ts[0].down else None)
-                has[j][role] = True
-
-        T: Dict[int, Optional[torch.Tensor]] = {}
-        specs = tails_for(-2)
-        specs1 = tails_for(-1)
-        need_main = len(specs1) < len(all_consumers(-1)) or n == 0
-        keep1 = need_main or not specs1
-        # Round 5: stem3d0 and stem3d1 as ONE call whose second kernel expands stem3d0's output from the variant planes in its own
-        # staging (ops.costvol_stem_conv3d): when nothing but stem3d1 and fused tails reads T[-2], that 164 MB tensor is never written.
-        fuse_stems = (x is None and ops.stem_fusion_enabled() and n >= 1
-                      and ((adt == torch.float32 and ops.get_conv_precision() == "f16x3") or adt == torch.bfloat16)
-                      and (0, 0, False) in fusable(-2) and stem0.conv.out_channels == 12 and stem1._geometry() == 3 and not stem1._small()
-                      and ops.costvol_stem_conv3d_supported(features[0].shape[1], 12, stem1.conv.out_channels, B, *vol,
-                                                            ntail=len(flat(specs1) or []), dtype=adt))
-        self.last_g4_plan["stems_fused"] = bool(fuse_stems)
-        if fuse_stems:
+        T: Dict[int, Optional[torch.Tensor]] = {-2: None}
+        t0, t1 = tails(-2), tails(-1)
+        if plan.stems_fused:
+            # stem3d0 and stem3d1 as ONE call whose second kernel expands stem3d0's output from the variant planes in its own staging
+            # (ops.costvol_stem_conv3d): nothing but stem3d1 and fused tails reads T[-2], so that 164 MB tensor is never written
             _w0, scale0, shift0 = stem0.prepared()
             wk1, scale1, shift1 = stem1.prepared()
             cout1 = stem1.conv.out_channels
-            # cell 0's pre_preprocess (the one tail on stem3d0's output) in the four idle rows of stem3d1's 12-channel matrix product
-            t0s = flat(specs)
-            rows = ops.stem_tail_rows_enabled() and cout1 == 12 and t0s is not None and len(t0s) == 1 and t0s[0].weight2d.shape[0] == 4
-            if rows:
-                tmod = cells[0].pre_preprocess
-                key = (stem1.stamp(), tmod.stamp())
+            if plan.stem_tail_rows:
+                # cell 0's pre_preprocess (the one tail on stem3d0's output) in the four idle rows of stem3d1's 12-channel matrix product
+                key = (stem1.stamp(), cells[0].pre_preprocess.stamp())
                 hit = getattr(stem1, "_rows_cache", None)
                 if hit is None or hit[0] != key:
                     with torch.no_grad():
-                        hit = (key, ops.conv3d_k3_pack(ops.stem_tail_rows_weight(stem1.conv.weight.detach(), t0s[0].weight2d)))
+                        hit = (key, ops.conv3d_k3_pack(ops.stem_tail_rows_weight(stem1.conv.weight.detach(), t0[0].weight2d)))
                     stem1._rows_cache = hit
                 wk1 = hit[1]
-            self.last_g4_plan["stem_tail_rows"] = bool(rows)
-            out1 = torch.empty((B, cout1) + vol, device=dev, dtype=adt) if keep1 else None
-            ops.costvol_stem_conv3d(features[0], features[1], self.maxdisp, stem0.costvol_variants(), 12, scale0, shift0, stem0.relu, flat(specs),
+            out1 = torch.empty((B, cout1) + sizes[-1], device=dev, dtype=ref.dtype) if keep1 else None
+            ops.costvol_stem_conv3d(features[0], features[1], self.maxdisp, stem0.costvol_variants(), 12, scale0, shift0, stem0.relu, t0,
                                     wk1, cout1, scale1, shift1, stem1.relu, out1, [4 * g for g in range(ops.packed_groups(cout1))],
-                                    tails=flat(specs1), store_main=keep1, tail0_rows=bool(rows))
-            T[-2] = None
-            settle(-2, specs, True, None)
+                                    tails=t1, store_main=keep1, tail0_rows=plan.stem_tail_rows)
         else:
             # stem3d0: its output also feeds stem3d1 (3x3x3), so it is materialised
             if x is None:
-                T[-2] = stem0.forward_costvol(features[0], features[1], self.maxdisp, tails=flat(specs), out_g4=t2_g4)
+                T[-2] = stem0.forward_costvol(features[0], features[1], self.maxdisp, tails=t0, out_g4=plan.stem0_g4)
             else:
-                T[-2] = stem0(x, tails=flat(specs))
-            settle(-2, specs, True, T[-2])
-            # stem3d1
-            out1 = stem1(T[-2], tails=flat(specs1), store_main=keep1, x_g4=t2_g4)
+                T[-2] = stem0(x, tails=t0)
+            out1 = stem1(T[-2], tails=t1, store_main=keep1, x_g4=plan.stem0_g4)
         T[-1] = out1 if keep1 else None
-        settle(-1, specs1, True, out1)
-        def shared_pre(i):
-            """Cells i and i+1 both resample T[i-1] (the `prev` of one, the `prev_prev` of the other) to the SAME size: cell i's two
-            1x1x1 convs and cell i+1's pre_preprocess as ONE launch — T[i-1] is gathered by both in the same launch (the second gather
-            hits the L2 the first one filled) and cell i+1 keeps a plain 1x1x1 launch for its other input."""
-            j = i + 1
-            if j >= n or any(has.get(i, (False, False))) or has.get(j, [False, False])[0] or sizes[i] != sizes[j]:
-                return
-            s0, s1 = T.get(i - 2), T.get(i - 1)
-            ci, cj = cells[i], cells[j]
-            if s0 is None or s1 is None or s0.shape[1] == ci.C_out or s1.shape[1] == cj.C_out or tuple(s1.shape[2:]) == sizes[i]:
-                return
-            if len({s0.dtype, s1.dtype, cdt[i], cdt[j]}) > 1:
-                return        # (mixed storage: the crossing launches stay with their cells)
-            if any(_volume(sizes[i]) > _volume(t.shape[2:]) for t in (s0, s1)):
-                return        # an up-sampling input runs conv-first (two launches): stays with its cell
-            for k in (i, j):
-                if k not in pre:
-                    pre[k] = torch.empty((B, 2 * cells[k].C_out) + sizes[k], device=dev, dtype=cdt[k])
-                    has[k] = [False, False]
-            ops.conv3d_k1_resample_multi([(s0,) + ci.pre_preprocess.prepared() + (ci.pre_preprocess.relu, pre[i], 0),
-                                          (s1,) + ci.preprocess.prepared() + (ci.preprocess.relu, pre[i], ci.C_out),
-                                          (s1,) + cj.pre_preprocess.prepared() + (cj.pre_preprocess.relu, pre[j], 0)], sizes[i])
-            has[i] = [True, True]
-            has[j][0] = True
-
-        for i, c in enumerate(cells):
-            shared_pre(i)
-            specs = tails_for(i)
-            need_main = i == n - 1 or len(specs) < len(all_consumers(i))   # the head reads the last cell's output
-            cat, applied = c._run(T[i - 2], T[i - 1], pre=pre.get(i), pre_has=tuple(has.get(i, (False, False))),
-                                  tails=flat(specs), store_main=need_main, size=sizes[i], pre_g4=g4[i], dtype=cdt[i])
-            settle(i, specs, applied, cat)
-            T[i] = cat
+        for i, (c, cp) in enumerate(zip(cells, plan.cells)):
+            if cp.shared_pre:
+                # Cells i and i+1 both resample T[i-1] (the `prev` of one, the `prev_prev` of the other) to the SAME size: cell i's two
+                # 1x1x1 convs and cell i+1's pre_preprocess as ONE launch — T[i-1] is gathered by both in the same launch (the second
+                # gather hits the L2 the first one filled) and cell i+1 keeps a plain 1x1x1 launch for its other input
+                cj = cells[i + 1]
+                ops.conv3d_k1_resample_multi([(T[i - 2],) + c.pre_preprocess.prepared() + (c.pre_preprocess.relu, buf(i), 0),
+                                              (T[i - 1],) + c.preprocess.prepared() + (c.preprocess.relu, buf(i), c.C_out),
+                                              (T[i - 1],) + cj.pre_preprocess.prepared() + (cj.pre_preprocess.relu, buf(i + 1), 0)], sizes[i])
+            T[i] = c._run(T[i - 2], T[i - 1], cp, pre.get(i), tails(i) if cp.tails else None)
+            if not cp.tails:      # a producer that is not one dual launch: its would-be tails run as plain 1x1x1 launches
+                for (j, role, down) in plan.consumers[i]:
+                    mod, dst, ch0 = unit(j, role)
+                    mod(T[i], out=dst, out_ch0=ch0, resample_to=sizes[j] if down else None)
             T.pop(i - 2, None)
         return T[n - 1]
 

@@ -342,3 +342,116 @@ def test_g4_layout_helpers_round_trip():
     flat = g.reshape(2, -1)
     base = ((1 * 3 + 1) * 4 + 2) * 5 + 3
     assert torch.equal(flat[0, 4 * base:4 * base + 4], t[0, 4:8, 1, 2, 3])
+
+
+# ---- the fused executor's plan (rag_amd.modules._plan_chain): decisions only, so it is checked without a GPU.  The expected values are
+# the ones the GPU tests assert on the running executor (test_matchingnet_g4_plan_and_bitwise, ..._bf16_storage_bitwise,
+# test_matchingnet_mixed_storage_plan).
+MIXED_ROWS = np.array([[0, 1], [1, 0], [3, 0], [2, 1], [8, 1], [6, 0]])      # (SURVEY 8 A6's unsorted probe rows, tools/fuzz_fused.py)
+
+
+def _chain_plan(rows, fea_shape, maxdisp, dtype=torch.float32, folded=True):
+    import rag_amd
+    from rag_amd.modules import _plan_chain
+    net = rag_amd.MatchingNet(rag_amd.Genotype(rows, None, rows, None), maxdisp=maxdisp).eval()
+    cells = [c[0] for c in net.cells_3d]
+    B, C, h, w = fea_shape
+    return cells, _plan_chain(net.stem3d0[0], net.stem3d1[0], cells, B, C if folded else 2 * C, (maxdisp // 3, h, w), dtype, folded)
+
+
+def _switches(ops, g4=True, fuse=True, rows=True, deep=True):
+    ops.set_g4(g4)
+    ops.set_stem_fusion(fuse)
+    ops.set_stem_tail_rows(rows)
+    ops.set_bf16_deep_fp32(deep)
+
+
+@pytest.mark.parametrize("fea,maxdisp", [((2, 12, 128, 416), 192), ((2, 12, 64, 128), 96)])
+def test_chain_plan_g4_and_fused_stems_fp32(built_lib, fea, maxdisp):
+    from rag_amd import ops
+    try:
+        with ops.conv_precision("f16x3"):
+            for g4, fuse in ((True, True), (True, False), (False, False), (False, True)):
+                _switches(ops, g4, fuse, rows=False)
+                _cells, plan = _chain_plan(O.ALL_CONV, fea, maxdisp)
+                assert plan.stem0_g4 == g4 and [cp.g4 for cp in plan.cells[:3]] == [g4] * 3, plan
+                assert not any(cp.g4 for cp in plan.cells[3:])
+                assert plan.stems_fused == fuse and not plan.stem_tail_rows
+                assert plan.stored[-2] == (not fuse)
+            _switches(ops)
+            _cells, plan = _chain_plan(O.ALL_CONV, fea, maxdisp)
+            assert plan.stems_fused and plan.stem_tail_rows and plan.stem0_g4
+            # the headline's fusion: stem3d1 and cells 0, 1 live only in their consumers' tails; cells 1 / 2 feed cell 3 one level down
+            assert [plan.stored[i] for i in range(-2, 3)] == [False, False, False, False, True]
+            assert plan.consumers[-2] == ((0, 0, False),) and plan.consumers[-1] == ((0, 1, False), (1, 0, False))
+            assert plan.consumers[1] == ((2, 1, False), (3, 0, True)) and plan.consumers[2] == ((3, 1, True),)
+            assert set(plan.sizes) == set(plan.cdt) == set(range(-2, 8)) and plan.sizes[-2] == (maxdisp // 3,) + fea[2:]
+            # stem3d0 on a materialised cost volume: its output feeds more than tails, nothing of the stems is fused or G4
+            _cells, plan = _chain_plan(O.ALL_CONV, fea, maxdisp, folded=False)
+            assert not plan.stems_fused and not plan.stem_tail_rows and not plan.stem0_g4 and plan.stored[-2]
+    finally:
+        _switches(ops)
+
+
+def test_chain_plan_g4_bf16_storage(built_lib):
+    from rag_amd import ops
+    try:
+        for g4, fuse in ((True, True), (True, False), (False, False), (False, True)):
+            _switches(ops, g4, fuse, rows=False)
+            _cells, plan = _chain_plan(O.ALL_CONV, (2, 12, 72, 132), 96, torch.bfloat16)
+            assert [cp.g4 for cp in plan.cells[:3]] == [g4] * 3 and not any(cp.g4 for cp in plan.cells[3:]), plan
+            assert plan.stems_fused == fuse
+    finally:
+        _switches(ops)
+
+
+def test_chain_plan_mixed_storage(built_lib):
+    """bf16 inputs: the three full-resolution cells bf16, every later cell fp32 (ops.set_bf16_deep_fp32); switched off: every cell bf16."""
+    from rag_amd import ops
+    bf, f32 = torch.bfloat16, torch.float32
+    try:
+        _switches(ops)
+        _cells, plan = _chain_plan(O.ALL_CONV, (1, 12, 48, 72), 48, bf)
+        assert [plan.cdt[i] for i in range(-2, 8)] == [bf] * 5 + [f32] * 5
+        assert [cp.dtype for cp in plan.cells] == [bf] * 3 + [f32] * 5
+        assert [plan.sizes[i] == (16, 48, 72) for i in range(8)] == [True] * 3 + [False] * 5
+        _switches(ops, deep=False)
+        _cells, plan = _chain_plan(O.ALL_CONV, (1, 12, 48, 72), 48, bf)
+        assert all(plan.cdt[i] == bf for i in range(-2, 8))
+        _cells, plan = _chain_plan(O.ALL_CONV, (1, 12, 48, 72), 48, f32)
+        assert all(plan.cdt[i] == f32 for i in range(-2, 8))
+    finally:
+        _switches(ops)
+
+
+def test_chain_plan_strict_fp32_precision_has_no_g4_and_no_fused_stems(built_lib):
+    from rag_amd import ops
+    try:
+        _switches(ops)
+        with ops.conv_precision("fp32"):
+            _cells, plan = _chain_plan(O.ALL_CONV, (2, 12, 128, 416), 192)
+        assert not plan.stem0_g4 and not any(cp.g4 for cp in plan.cells) and not plan.stems_fused and not plan.stem_tail_rows
+    finally:
+        _switches(ops)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("rows,any_dual", [(O.ALL_CONV, True), (O.ALL_SKIP, False), (MIXED_ROWS, False)])
+def test_chain_plan_dual_cells_by_genotype(built_lib, rows, any_dual, dtype):
+    """A cell is one dual launch exactly when both inputs feed conv branches into every new state and nothing else does; only such a
+    cell takes tails or a G4 buffer."""
+    from rag_amd import ops
+    from rag_amd.modules import _ConvBR
+    try:
+        _switches(ops)
+        for fea, maxdisp in (((2, 12, 128, 416), 192), ((1, 12, 48, 72), 48)):
+            cells, plan = _chain_plan(rows, fea, maxdisp, dtype)
+            assert len(plan.cells) == 8
+            for c, cp in zip(cells, plan.cells):
+                contribs = c._contributions()
+                expect = all([src for src, _op in lst] == [0, 1] and all(isinstance(op, _ConvBR) for _s, op in lst) for lst in contribs.values())
+                assert cp.dual == expect == any_dual
+                assert cp.dual or not (cp.g4 or cp.tails)
+                assert cp.store_main or cp.tails      # a concat nobody stores went to tails
+    finally:
+        _switches(ops)
