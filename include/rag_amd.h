@@ -629,6 +629,41 @@ int ragmi_sgd_clip_step(void* param, void* grad, void* momentum_buf, int64_t n, 
                         float max_norm, int first_step, void* workspace, void* norm_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * Batch preparation on the device (the reference's loaders: src/dataloaders/data_io.py:6-13, stereo_dataset.py:35-38, 57-121;
+ * src_self/dataloaders/sceneflow_driving_dataset.py:53-70), ONE launch per batch:
+ *   left_u8, right_u8 [B,Hs,Ws,3] uint8 (HWC, as decoded)  ->  left, right [B,3,H,W] fp32
+ *   gt [B,Hs,Ws] uint16 (RAGMI_GT_U16) or fp32 (RAGMI_GT_F32)  ->  gt_out [B,H,W] fp32 = (float)gt * gt_scale (1/256 for KITTI-style
+ *   16-bit disparities: exact)
+ * Output pixel (y, x) of sample b reads source pixel (y + origin[b,0], x + origin[b,1]) and is 0 where that falls outside the
+ * source; origin: device int32 [B,2].  A training crop is origin = (y1, x1); the evaluation pad is origin = (-top_pad, 0) (the pad
+ * is 0 AFTER normalisation, as the reference pads).  Image values are ToTensor + Normalize in fp32, bit for bit:
+ * ((float)u / 255 - mean_c) / std_c with two IEEE divisions.  With stats_source (and stats_left, and stats_right when there is a
+ * right view; each float64 [B,3,2] = (mean, std of column stds) per channel, as ragmi_color_stats writes) every byte first goes
+ * through transfer_color's float64 sequence t = u/255; t -= tm; t /= ts/ss; t += sm; clip(t,0,1); trunc(t*255), and that level is
+ * normalised.  ts == 0 gives an unspecified level (the reference divides by zero), never a fault.  right_u8/right and gt/gt_out
+ * may be NULL in pairs.  RAGMI_EINVAL: null pointer, non-positive size, misaligned pointer; RAGMI_EUNSUPPORTED: gt_dtype.
+ * No allocation, no host synchronisation, no host copy: the launch replays with new origins and new bytes. */
+#define RAGMI_GT_F32 0
+#define RAGMI_GT_U16 1
+int ragmi_prep_batch(const void* left_u8, const void* right_u8, const void* gt, int gt_dtype, float gt_scale, const void* origin,
+                     void* left, void* right, void* gt_out, int B, int Hs, int Ws, int H, int W, float mean0, float mean1, float mean2,
+                     float std0, float std1, float std2, const void* stats_left, const void* stats_right, const void* stats_source,
+                     void* stream);
+
+/* Colour statistics of transfer_color for img_u8 [B,Hs,Ws,3] uint8: stats [B,3,2] float64 = per channel the mean of u/255 and the
+ * population std over columns of the per-column population stds (numpy's x.std(0).std(0)).  The column sums of u and u^2 are
+ * accumulated exactly in 64-bit integers; the rest is double, reduced in a fixed order.  workspace:
+ * ragmi_color_stats_workspace_elems(B,Hs,Ws) 8-byte elements, 8-byte aligned, scratch.  Two launches, no atomics (bitwise
+ * reproducible), no memset, no host synchronisation. */
+int64_t ragmi_color_stats_workspace_elems(int B, int Hs, int Ws);
+int ragmi_color_stats(const void* img_u8, int B, int Hs, int Ws, void* workspace, void* stats, void* stream);
+
+/* transfer_color as an image: out_u8 [B,H,W,3] uint8 from target_u8 with statistics stats_target against stats_source (both
+ * float64 [B,3,2]); the same per-byte sequence as ragmi_prep_batch's.  One launch. */
+int ragmi_color_transfer(const void* target_u8, const void* stats_target, const void* stats_source, void* out_u8, int B, int H, int W,
+                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * Host-side guard for captured steps (no device work): counts the nodes of a captured hipGraph_t by kind.  A captured training
  * step must consist of kernel nodes only: on ROCm 7.2 memset / memcpy NODES of an instantiated graph were corrupted by memcpys
  * issued on the null stream between two replays, so rag_amd.train.GraphedTrainStep refuses a capture for which

@@ -146,6 +146,12 @@ SIGNATURES = {
     "ragmi_silog_loss_workspace_elems": (c_int, [ctypes.c_longlong]),
     "ragmi_silog_loss_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ragmi_silog_loss_bwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ragmi_prep_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ragmi_color_stats_workspace_elems": (c_int64, [c_int, c_int, c_int]),
+    "ragmi_color_stats": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ragmi_color_transfer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ragmi_disp_softargmin_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_disp_softargmin_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p]),
