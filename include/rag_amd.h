@@ -176,6 +176,20 @@ int ragmi_down2_tail_supported(int D, int H, int W);
 /* bit mask: 1 = this call accepts a G4 input, 2 = it can write G4 full-resolution tails (arguments as ragmi_conv3d_k3_uses_x3) */
 int ragmi_conv3d_k3_g4_caps(int Cin, int Cout, int B, int D, int H, int W, int nset, int ntail, int ndown, int dtype);
 
+/* Quarter store (round 6).  store_main bit 1 (RAGMI_STORE_QUARTER_ROWS, with bit 0) of ragmi_conv3d_k3_dual_fwd_ex: the ONLY reader of the
+ * main output y is a x0.25 trilinear align_corners=True resample (F.interpolate to [D/4, H/4, W/4], Cell_3d's pre_preprocess input two
+ * levels down, rag_model.py:146-155).  That resample reads two source indices per output and axis, both inside the aligned group
+ * [4X, 4X + 3], so the launch writes only the planes and rows that are some output's source and leaves every other (plane, row) of y
+ * UNWRITTEN; what it writes is bit for bit what the full store writes there.  A PRIVATE contract of the fused executor, like G4.
+ * Taken only where ragmi_conv3d_k3_quarter_store_supported says so (RAGMI_EUNSUPPORTED otherwise): RAGMI_F32X3, a 12-channel level-3
+ * dual launch with down-sampling tails and no full-resolution ones, D, H, W multiples of 4 with D, H <= 256, and a work list whose
+ * items (half items included) all start on a multiple of 4 planes and span at most 32.  Arguments as ragmi_conv3d_k3_g4_caps. */
+#define RAGMI_STORE_QUARTER_ROWS 2
+int ragmi_conv3d_k3_quarter_store_supported(int Cin, int Cout, int B, int D, int H, int W, int nset, int ntail, int ndown, int dtype);
+/* used[i] (n_in bytes) = 1 where source index i of an axis of n_in = 4 * n_out voxels is read by that resample (the set the launch above
+ * writes, per axis: planes and rows); returns 0 when n_in is no multiple of 4, below 8, or a source pair leaves its aligned group. */
+int ragmi_quarter_store_rows(int n_in, unsigned char* used);
+
 /*
  * ragmi_conv3d_k3_fwd / ragmi_conv3d_k3_dual_fwd with up to two full-resolution tails (plus up to two down-sampling ones).  store_main = 0 skips writing the 3x3x3
  * result itself (only the tails consume it).  Tails need Cout in {4, 8, 12, 16} (all channels in one workgroup).

@@ -54,6 +54,8 @@ SIGNATURES = {
                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_conv3d_k3_uses_x3": (c_int, [c_int] * 10),
     "ragmi_conv3d_k3_g4_caps": (c_int, [c_int] * 10),
+    "ragmi_conv3d_k3_quarter_store_supported": (c_int, [c_int] * 10),
+    "ragmi_quarter_store_rows": (c_int, [c_int, ctypes.POINTER(ctypes.c_ubyte)]),
     "ragmi_conv3d_k3_packed_elems": (c_int64, [c_int, c_int]),
     "ragmi_conv3d_k3_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "ragmi_conv3d_k3_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,

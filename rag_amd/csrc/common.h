@@ -137,7 +137,7 @@ struct LinIdx {
   int i0, i1;
   float w0, w1;
 };
-__device__ __forceinline__ LinIdx lin_index(int dst, int in_size, int out_size, float scale, int align_corners) {
+__host__ __device__ __forceinline__ LinIdx lin_index(int dst, int in_size, int out_size, float scale, int align_corners) {
   // ATen's arithmetic, bit for bit (checked against torch CPU on this image, round 4: 100 % identical outputs in 1-D):
   //   align_corners=True : src = fl(scale * dst); i0 = (int)src; lambda = src - i0   (the product is ROUNDED before it is used twice)
   //   align_corners=False: src = fma(scale, dst + 0.5, -0.5)                          (one rounding: the CPU build contracts it)

@@ -267,6 +267,11 @@ extern "C" int ragmi_conv3d_k3_dual_fwd_ex(const void* x, int64_t x_bstride, int
   a.nchunks[1] = (CinB + CK - 1) / CK;
   const int rt = fill_tails(a, store_main, ntail, tails, Cout);
   if (rt != RAGMI_OK) return rt;
+  if (store_main & RAGMI_STORE_QUARTER_ROWS) {      // (fill_tails keeps bit 0 only: no other entry point takes the flag)
+    RAGMI_REQUIRE((store_main & 1) && x3_quarter_store_ok(a, 2, dtype), RAGMI_EUNSUPPORTED,
+                  "conv3d_k3_dual: this call does not take RAGMI_STORE_QUARTER_ROWS (ragmi_conv3d_k3_quarter_store_supported)");
+    a.store_main |= RAGMI_STORE_QUARTER_ROWS;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int ng = (Cout + 3) / 4;
   const bool bf = dtype == RAGMI_BF16;
@@ -314,6 +319,22 @@ extern "C" int ragmi_conv3d_k3_g4_caps(int Cin, int Cout, int B, int D, int H, i
   else a.nchunks[0] = (Cin + CK - 1) / CK;
   a.store_main = 1;
   return x3_g4_caps(a, nset, dtype);
+}
+
+extern "C" int ragmi_conv3d_k3_quarter_store_supported(int Cin, int Cout, int B, int D, int H, int W, int nset, int ntail, int ndown, int dtype) {
+  using namespace ragmi;
+  if (Cin <= 0 || Cout <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || nset != 2 || Cin % (2 * CK)) return 0;
+  K3Args a{};
+  a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.ntail = ntail; a.ndown = ndown;
+  for (int t = 0; t < 2; ++t) a.tail_cout[t] = a.down_cout[t] = 4;
+  for (int g = 0; g < (Cout + 3) / 4 && g < RAGMI_MAX_GROUPS; ++g) a.y_ch[g] = 4 * g;
+  a.nchunks[0] = a.nchunks[1] = Cin / (2 * CK);
+  a.store_main = 1;
+  return x3_quarter_store_ok(a, nset, dtype) ? 1 : 0;
+}
+
+extern "C" int ragmi_quarter_store_rows(int n_in, unsigned char* used) {
+  return (used != nullptr && ragmi::quarter_store_rows(n_in, used)) ? 1 : 0;
 }
 
 extern "C" int ragmi_conv3d_k3_plan(int Cout, int B, int D, int H, int W, int nset, int32_t* log_tx,

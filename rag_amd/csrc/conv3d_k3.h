@@ -75,7 +75,7 @@ struct K3Args {
   // up to two consumer 1x1x1 ConvBR_3d fused into the epilogue ("tails"): y_t[j] = act(bn_t(sum_c W_t[j][c] * out[c])).
   // Needs every output channel of a voxel in one lane: one split (gridDim.y == 1), Cout == 4*G <= 16, tail Cout <= 4.
   int ntail;
-  int store_main;              // 0: the conv's own output is consumed only by the tails and is not written
+  int store_main;              // 0: the conv's own output is consumed only by the tails and is not written; bit 1: RAGMI_STORE_QUARTER_ROWS
   const float* tail_w[2];      // [tail_cout][Cout] row-major
   const float* tail_scale[2];
   const float* tail_shift[2];
@@ -626,6 +626,8 @@ int c1_launch(const K3Args& k, int dtype, int y_dtype, hipStream_t st);
 int pack_both(const float* w, float* packed, int64_t total_k3, int Cout, int Cin, int transpose, int planar, bool all, hipStream_t s);
 bool x3_eligible(const K3Args& a, int nset, int dtype);
 int x3_g4_caps(const K3Args& a, int nset, int dtype);      // G4 forms (include/rag_amd.h) the kernel this call lands on takes
+bool x3_quarter_store_ok(K3Args a, int nset, int dtype);      // RAGMI_STORE_QUARTER_ROWS (include/rag_amd.h): the launch this call lands on takes it
+bool quarter_store_rows(int n_in, unsigned char* used);       // the source indices a x0.25 align_corners=True resample reads on one axis
 struct X3StemSrc;
 int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* src = nullptr);
 // argument marshalling of the 3x3x3 entry points (conv3d.hip), shared with ragmi_costvol_stem_conv3d_fwd (costvol_stem.hip)

@@ -1184,19 +1184,9 @@ extern "C" __attribute__((visibility("default"))) int ragmi_diag_x3_stamp_buffer
 }
 #endif
 
-// a: as filled for the fp32 kernel (wp[s] = packed weights: fp32-MFMA section followed by the bf16x3 fragments)
-int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* src) {
-#ifdef RAGMI_DIAG
-  static const int diag_x3 = [] { const char* v = getenv("RAGMI_X3_DIAG"); return v ? atoi(v) : 0; }();   // 1 no stores, 2 no MFMA block, 4 no commit, 8 no loads, 16 operand reads at one address, 32 in-kernel stamps, 64 / 128 (quad-ring kernel) no finishing step / no parking of the down-sampling tails
-  a.relu |= diag_x3 << 8;
-#endif
-  X3Extra e{};
-  if (src) e.src = *src;
-  x3_weight_sections(e, a, nset, dtype);
-  if (src && src->tail_rows) { K3Args t16 = a; t16.Cout = 16; x3_weight_sections(e, t16, nset, dtype); }      // (the caller's pack is a 16-channel one: RAGMI_TAIL_ROWS)
-  const int ncg = a.nchunks[0] + (nset == 2 ? a.nchunks[1] : 0), ncgs = ncg / nset, nsls = (ncgs * 27 + 7) / 8, nsl = nset * nsls;
-  a.tiles_x = (int)ceil_div(a.W, X3_TX); a.tiles_y = (int)ceil_div(a.H, X3_TY);
-  const int ncog = (a.Cout + 15) / 16;
+// The z-marching work list of a launch (a.tiles_x / a.tiles_y set): depth segments per column, the groups the list is dealt in and the
+// pairs cut into half items.  Its own function since round 6: the quarter-store predicate (x3_quarter_store_ok) asks where items start.
+static void x3_schedule(const K3Args& a, int dtype, int ncog, X3Extra& e) {
   // depth segments: enough independent (column, segment) work items to fill several workgroups per CU, at least 8 planes each.
   // (Measured on the level-3 volumes, round 2, both builds on one box: 8 segments 1.214 ms per step; 4: 1.253, 5: 1.262, 6: 1.213,
   // 7: 1.256, 10: 1.305, 13: 1.224, 16: 1.299.  A model that minimises rounds x (planes + 2 halo planes) does not predict this.)
@@ -1232,6 +1222,73 @@ int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* sr
     if (e.seg_len % 4 != 0 || (a.D - (e.nseg - 1) * e.seg_len) % 4 != 0) e.nsplit = 0;
     e.dsd = lin_scale(a.D, a.D / 2, 1); e.dsh = lin_scale(a.H, a.H / 2, 1); e.dsw = lin_scale(a.W, a.W / 2, 1);
   }
+}
+
+// Quarter store (round 6, include/rag_amd.h RAGMI_STORE_QUARTER_ROWS).  A main output whose only reader is a x0.25 trilinear
+// align_corners=True resample (cell i+2's pre_preprocess two levels down) is read at two source indices per output and axis, and
+// both lie inside the aligned group [4X, 4X + 3]: of every four planes and of every four rows at most two are ever read.  The launch
+// then skips the main store of every (plane, row) outside that set.  The set comes from the SAME lin_index the resample kernel
+// evaluates (conv_k1_resample_kernel), so what it reads is written, bit for bit what the full store wrote there.
+// used[i] = 1 for every source index i of an axis of n_in = 4 * n_out voxels that some output reads (null: only check); false when a
+// pair leaves its group.
+bool quarter_store_rows(int n_in, unsigned char* used) {
+  if (n_in < 8 || n_in % 4 != 0) return false;
+  const int n_out = n_in / 4;
+  const float scale = lin_scale(n_in, n_out, 1);
+  for (int i = 0; used && i < n_in; ++i) used[i] = 0;
+  for (int X = 0; X < n_out; ++X) {
+    const LinIdx l = lin_index(X, n_in, n_out, scale, 1);
+    if (l.i0 < 4 * X || l.i1 > 4 * X + 3 || l.i1 < l.i0) return false;
+    if (used) used[l.i0] = used[l.i1] = 1;
+  }
+  return true;
+}
+constexpr int XQ_QMAX = 256;      // planes / rows the launch's bit tables hold (X3Extra::qz, qy)
+// the launch `a` (tails filled in) can skip the rows a quarter-size consumer never reads: the fp32-storage level-3 dual launch with
+// down-sampling tails (conv3d_x3q_kernel<2, 2, *, false>), 12 output channels, every axis a multiple of 4 and every work item starting on
+// a multiple of 4 planes (the half items included) and at most 32 planes long (one 32-bit plane mask per item)
+bool x3_quarter_store_ok(K3Args a, int nset, int dtype) {
+  if (dtype != RAGMI_F32X3 || nset != 2 || a.Cout != 12 || a.ndown == 0 || a.ntail != 0 || !a.store_main) return false;
+  if (x2d_eligible(a, nset, dtype) || x3d_eligible(a, nset, dtype) || !x3_eligible(a, nset, dtype)) return false;
+#ifdef RAGMI_NO_X3Q
+  return false;
+#endif
+  if (!xq_takes(a, nset, dtype)) return false;
+  if (a.D % 4 || a.H % 4 || a.W % 4 || a.D > XQ_QMAX || a.H > XQ_QMAX) return false;
+  if (!quarter_store_rows(a.D, nullptr) || !quarter_store_rows(a.H, nullptr) || !quarter_store_rows(a.W, nullptr)) return false;
+  X3Extra e{};
+  a.tiles_x = (int)ceil_div(a.W, X3_TX); a.tiles_y = (int)ceil_div(a.H, X3_TY);
+  x3_schedule(a, dtype, (a.Cout + 15) / 16, e);
+  const int last = a.D - (e.nseg - 1) * e.seg_len;
+  if (e.seg_len % 4 != 0 || e.seg_len > 32) return false;
+  if (e.nsplit > 0 && (e.seg_len % 8 != 0 || last % 8 != 0)) return false;      // a half item starts at zs + ceil(len / 2)
+  return true;
+}
+
+// a: as filled for the fp32 kernel (wp[s] = packed weights: fp32-MFMA section followed by the bf16x3 fragments)
+int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* src) {
+#ifdef RAGMI_DIAG
+  static const int diag_x3 = [] { const char* v = getenv("RAGMI_X3_DIAG"); return v ? atoi(v) : 0; }();   // 1 no stores, 2 no MFMA block, 4 no commit, 8 no loads, 16 operand reads at one address, 32 in-kernel stamps, 64 / 128 (quad-ring kernel) no finishing step / no parking of the down-sampling tails
+  a.relu |= diag_x3 << 8;
+#endif
+  X3Extra e{};
+  if (src) e.src = *src;
+  x3_weight_sections(e, a, nset, dtype);
+  if (src && src->tail_rows) { K3Args t16 = a; t16.Cout = 16; x3_weight_sections(e, t16, nset, dtype); }      // (the caller's pack is a 16-channel one: RAGMI_TAIL_ROWS)
+  const int ncg = a.nchunks[0] + (nset == 2 ? a.nchunks[1] : 0), ncgs = ncg / nset, nsls = (ncgs * 27 + 7) / 8, nsl = nset * nsls;
+  a.tiles_x = (int)ceil_div(a.W, X3_TX); a.tiles_y = (int)ceil_div(a.H, X3_TY);
+  const int ncog = (a.Cout + 15) / 16;
+  x3_schedule(a, dtype, ncog, e);
+  if (a.store_main & RAGMI_STORE_QUARTER_ROWS) {
+    RAGMI_REQUIRE(!src && x3_quarter_store_ok(a, nset, dtype), RAGMI_EUNSUPPORTED,
+                  "conv3d_x3: this launch does not take RAGMI_STORE_QUARTER_ROWS (ragmi_conv3d_k3_quarter_store_supported)");
+    unsigned char used[XQ_QMAX];
+    quarter_store_rows(a.D, used);
+    for (int i = 0; i < a.D; ++i) e.qz[i >> 5] |= (unsigned)used[i] << (i & 31);
+    quarter_store_rows(a.H, used);
+    for (int i = 0; i < a.H; ++i) e.qy[i >> 5] |= (unsigned)used[i] << (i & 31);
+  }
+  const int64_t per_sample = (int64_t)a.tiles_x * a.tiles_y * e.nseg;
   const int64_t nwork = (int64_t)a.B * e.ngrp * (e.grp + e.nsplit);
   RAGMI_REQUIRE(nwork < (1ll << 31) && per_sample < (1ll << 28), RAGMI_EUNSUPPORTED, "conv3d_x3: too many tiles");
   e.nwork = (int)nwork;

@@ -53,8 +53,11 @@ extern "C" __attribute__((visibility("default"))) int ragmi_diag_x3q_stamp_buffe
 // access — a halo voxel is one buffer_load_dwordx4 per group instead of four dword loads, a tail one global_store_dwordx4 instead of
 // four dword stores into four planes (64-byte segments).  The vector memory path costs per INSTRUCTION here (the plane step issued
 // ~190 of them per workgroup, ~20 cycles each with two workgroups per CU: MI355X_MICROARCH.md, store tail; profiles/r05_x3_stamps.md).
+// QS (round 6, RAGMI_STORE_QUARTER_ROWS): the main output's only reader is a x0.25 align_corners=True resample — the main store of a
+// plane / a row that is no output's source index (bit tables e.qz / e.qy, from the resample kernel's own lin_index: x3_launch) is
+// skipped, 3/4 of that store's bytes.  Rows are waves here and planes are steps, so both tests are wave-uniform scalars.
 typedef unsigned xq_u32x4 __attribute__((ext_vector_type(4)));
-template <int NSET, int TAILS, bool G4X, bool G4T>
+template <int NSET, int TAILS, bool G4X, bool G4T, bool QS = false>
 __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3Extra e) {
   using T = float;
   constexpr int NCG = NSET, NSL = 4 * NSET;
@@ -318,6 +321,7 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
     }
   };
   int zs = 0;
+  unsigned qplanes = 0u, qrow = 0u;       // QS: bit k = plane zs + k of this item is stored (items span <= 32 planes); this wave's row is stored
   // destinations, per item: the main output as a 32-bit lane offset against a wave-uniform base (Cout * D * H * W < 2^31 elements is the
   // library's rule); the lane quarter's tail as a running 64-bit pointer (two tails may live in different tensors)
   unsigned yoff[X3_NT];
@@ -361,7 +365,7 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
     }
 #pragma unroll
     for (int i = 0; i < X3_NT; ++i) {
-      if (a.store_main && inside[i] && g < ngroups && !(dg_nostore && v[i][0] != 12345.f)) {
+      if (a.store_main && (!QS || (qrow & (qplanes >> (z - zs)) & 1u)) && inside[i] && g < ngroups && !(dg_nostore && v[i][0] != 12345.f)) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[i][r]), yrs, (int)yoff[i], ybase + r * (int)DHW * (int)sizeof(T), 0);
@@ -510,6 +514,12 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
       inside[i] = gy < a.H && gx < a.W;
       yoff[i] = (unsigned)(my_ych * (int)DHW + gy * a.W + gx) * (unsigned)sizeof(T);
     }
+    if constexpr (QS) {
+      // (uniform indices said to be: the tables are read with scalar loads from the argument segment, once per item)
+      const int gyu = y0 + __builtin_amdgcn_readfirstlane(wave), zw = __builtin_amdgcn_readfirstlane(zs) >> 5;
+      qrow = (e.qy[(gyu >> 5) & 7] >> (gyu & 31)) & 1u;
+      qplanes = (unsigned)(((((unsigned long long)e.qz[(zw + 1) & 7]) << 32) | e.qz[zw & 7]) >> (zs & 31));
+    }
     if constexpr (TAILS) {
       T* const my_tail = static_cast<T*>(tsel ? a.tail_y[1] : a.tail_y[0]);
       const int64_t tb = tsel ? a.tail_bstride[1] : a.tail_bstride[0];
@@ -598,23 +608,29 @@ bool xq_takes(const K3Args& a, int nset, int dtype) {
   return dtype == RAGMI_F32X3 && a.Cout <= 16 && a.Cin * vol * 4 < (1ll << 31) && (ych + 4) * vol * 4 < (1ll << 31) && nset == 2 && a.nchunks[0] == 1 && a.nchunks[1] == 1;
 }
 
-template <int NSET, int TAILS, bool G4X, bool G4T>
+template <int NSET, int TAILS, bool G4X, bool G4T, bool QS = false>
 static int xq_launch_one(const K3Args& a, const X3Extra& e, dim3 grid, hipStream_t st) {
   static LaunchState state;
   const size_t lds = xq_lds_bytes(NSET, TAILS == 2);
-  const int slots = state.slots((const void*)conv3d_x3q_kernel<NSET, TAILS, G4X, G4T>, X3_THREADS, lds, 160 * 1024);
+  const int slots = state.slots((const void*)conv3d_x3q_kernel<NSET, TAILS, G4X, G4T, QS>, X3_THREADS, lds, 160 * 1024);
   if (slots <= 0) return fail(RAGMI_ELAUNCH, "conv3d_x3q: cannot raise the dynamic LDS limit");
   grid.x = (unsigned)std::max<int64_t>(1, std::min<int64_t>(grid.x, std::max(256, slots) / (int)grid.y));
 #ifdef RAGMI_DIAG
   static const int diag_grid = [] { const char* v = getenv("RAGMI_X3_GRID"); return v ? atoi(v) : 0; }();      // profiling builds: persistent grid size
   if (diag_grid > 0) grid.x = (unsigned)std::min<int64_t>(grid.x, diag_grid);
 #endif
-  hipLaunchKernelGGL((conv3d_x3q_kernel<NSET, TAILS, G4X, G4T>), grid, dim3(X3_THREADS), lds, st, a, e);
+  hipLaunchKernelGGL((conv3d_x3q_kernel<NSET, TAILS, G4X, G4T, QS>), grid, dim3(X3_THREADS), lds, st, a, e);
   return check_launch("conv3d_x3q");
 }
 template <int TAILS>
 static int xq_launch_layout(const K3Args& a, const X3Extra& e, dim3 grid, hipStream_t st) {
   const bool g4x = (a.relu & RAGMI_CONV_X_G4) != 0, g4t = a.tail_g4 != 0;
+  if (a.store_main & RAGMI_STORE_QUARTER_ROWS) {      // (x3_quarter_store_ok: down-sampling tails, no full-resolution ones)
+    if constexpr (TAILS == 2) {
+      if (!g4t) return g4x ? xq_launch_one<2, 2, true, false, true>(a, e, grid, st) : xq_launch_one<2, 2, false, false, true>(a, e, grid, st);
+    }
+    return fail(RAGMI_EUNSUPPORTED, "conv3d_x3q: RAGMI_STORE_QUARTER_ROWS needs down-sampling tails and no G4 tails");
+  }
   if constexpr (TAILS == 0) return g4x ? xq_launch_one<2, 0, true, false>(a, e, grid, st) : xq_launch_one<2, 0, false, false>(a, e, grid, st);
   else return g4x ? (g4t ? xq_launch_one<2, TAILS, true, true>(a, e, grid, st) : xq_launch_one<2, TAILS, true, false>(a, e, grid, st))
                   : (g4t ? xq_launch_one<2, TAILS, false, true>(a, e, grid, st) : xq_launch_one<2, TAILS, false, false>(a, e, grid, st));

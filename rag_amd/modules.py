@@ -496,7 +496,7 @@ class _Cell(nn.Module):
         a, b, whole = self.dual_branches(pre_has[0] or s0.shape[1] != C)
         if plan is None:
             plan = _CellPlan(size=self.out_size(s1.shape[2:]), dtype=s1.dtype, has=pre_has, g4=False, dual=whole, store_main=True, tails=False,
-                             shared_pre=False)
+                             shared_pre=False, quarter=False)
         # the trilinear resamples (rag_model.py:146-153) are fused into the 1x1x1 preprocess convs that consume them
         size = tuple(int(v) for v in plan.size)
         if not pre_has[0] and s0.shape[1] == C and tuple(s0.shape[2:]) != size:
@@ -584,7 +584,7 @@ class _Cell(nn.Module):
             pb, sb, hb = self._fused([op for _k, op in b])
             groups = [where[k][1] + 4 * g for k, _op in a for g in range(C // 4)]
             ops.conv3d_k3_dual(pre, C, pa, sa, ha, pb, sb, hb, C * len(a), True, where[a[0][0]][0], groups,
-                               tails=tails, store_main=plan.store_main, x_g4=plan.g4)
+                               tails=tails, store_main=plan.store_main, x_g4=plan.g4, quarter=plan.quarter)
             for j, branches in enumerate((a, b)):
                 for k, op in branches:
                     written[k] = True
@@ -669,11 +669,12 @@ _CELL3D_ARCH = ((4, 4, 4, 0), (4, 4, 4, 0), (4, 4, 4, 0), (4, 4, 8, -1),
 #   _CellPlan: size / dtype of the cell's s0|s1 buffer and of its output; has = which halves of that buffer are written before the cell
 #   runs (fused tails, shared_pre); g4 = the buffer is channel-group-interleaved; dual = one dual launch produces every new state
 #   (_Cell.dual_branches); store_main = the concat is written; tails = its consumers ride on that launch (else they run as plain 1x1x1
-#   launches behind it); shared_pre = its two 1x1x1 convs and cell i+1's pre_preprocess run as one launch in front of it.
+#   launches behind it); shared_pre = its two 1x1x1 convs and cell i+1's pre_preprocess run as one launch in front of it; quarter = its
+#   stored concat is read only by a x0.25 resample two cells on, and the launch skips the planes and rows that resample never reads.
 #   _ChainPlan: sizes[i], cdt[i] (storage type), consumers[i] = ((cell j, role, down), ...) fused onto T[i]'s producer, stored[i] for
 #   i = -2 .. n-1; cells = the _CellPlans; stem0_g4 = T[-2] is G4; stems_fused = both stems as one call (T[-2] never written);
 #   stem_tail_rows = cell 0's pre_preprocess in the idle rows of stem3d1's matrix product.
-_CellPlan = namedtuple("_CellPlan", "size dtype has g4 dual store_main tails shared_pre")
+_CellPlan = namedtuple("_CellPlan", "size dtype has g4 dual store_main tails shared_pre quarter")
 _ChainPlan = namedtuple("_ChainPlan", "sizes cdt consumers stored cells stem0_g4 stems_fused stem_tail_rows")
 
 
@@ -719,6 +720,9 @@ def _plan_chain(stem0, stem1, cells, B: int, C_fea: int, vol, adt: torch.dtype, 
         found = []
         for j, role in ((i + 1, 1), (i + 2, 0)):
             c = cells[j] if 0 <= j < n else None
+            # (a prev_prev edge across a resampling cell is at another size than T[i] and never rides as a tail.  Where that size is
+            # exactly a quarter — cell 4 on T[2] — the edge is served by the quarter store below instead: T[i] stays a stored tensor,
+            # but only the planes and rows that x0.25 resample reads are written)
             if c is None or (role == 0 and (c.C_prev_prev == c.C_out or (j > 0 and cells[j - 1].downup_sample != 0))):
                 continue
             if c.downup_sample == 0 and c.C_out == 4 and cdt[j] == cdt[i]:
@@ -768,6 +772,15 @@ def _plan_chain(stem0, stem1, cells, B: int, C_fea: int, vol, adt: torch.dtype, 
     # a main output is stored unless every reader is a tail of its producer (the head reads the last one)
     stored = {i: i == n - 1 or not tails[i] or len(consumers[i]) < sum(0 <= j < n for j in (i + 1, i + 2)) for i in range(-1, n)}
     stored[-2] = not stems_fused
+    # Quarter store: T[i] is stored for ONE reader, cell i+2's pre_preprocess behind a x0.25 trilinear resample (cell i+1, one level down,
+    # rides on T[i]'s producer as down-sampling tails), and its producer is the launch that can skip what that resample never reads
+    # (ops.quarter_store_supported: fp32 storage under f16x3, a 12-channel level-3 dual launch, aligned axes and work items)
+    quarter = {i: bool(ops.quarter_store_enabled() and 0 <= i and i + 2 < n and stored[i] and tails[i] and dual[i]
+                       and consumers[i] == ((i + 1, 1, True),) and cdt[i] == cdt[i + 2] == f32 and ops.get_conv_precision() == "f16x3"
+                       and cells[i + 2].C_prev_prev != cells[i + 2].C_out
+                       and tuple(4 * v for v in sizes[i + 2]) == tuple(sizes[i])
+                       and ops.quarter_store_supported(2 * cells[i].C_out, cout[i], B, *sizes[i], nset=2, ntail=0, ndown=ndown[i], dtype=cdt[i]))
+               for i in range(n)}
     has = [[False, False] for _ in cells]
     plans = []
     for i in range(-2, n):
@@ -781,7 +794,7 @@ def _plan_chain(stem0, stem1, cells, B: int, C_fea: int, vol, adt: torch.dtype, 
                       and _volume(sizes[i]) <= min(_volume(sizes[i - 2]), _volume(sizes[i - 1])))
             if shared:
                 has[i], has[j][0] = [True, True], True
-            plans.append(_CellPlan(sizes[i], cdt[i], tuple(has[i]), g4[i], dual[i], stored[i], tails[i], shared))
+            plans.append(_CellPlan(sizes[i], cdt[i], tuple(has[i]), g4[i], dual[i], stored[i], tails[i], shared, quarter[i]))
         for (j, role, _d) in consumers[i]:
             has[j][role] = True
     ro = MappingProxyType
@@ -882,7 +895,8 @@ class MatchingNet(nn.Module):
         plan = _plan_chain(stem0, stem1, cells, B, ref.shape[1], self._vol_size(x, features), ref.dtype, x is None)
         sizes, keep1 = plan.sizes, plan.stored[-1]
         self.last_g4_plan = {"pre": {j: cp.g4 for j, cp in enumerate(plan.cells)}, "stem0_out": plan.stem0_g4,      # (tests and tools read it)
-                             "stems_fused": plan.stems_fused, **({"stem_tail_rows": plan.stem_tail_rows} if plan.stems_fused else {})}
+                             "stems_fused": plan.stems_fused, **({"stem_tail_rows": plan.stem_tail_rows} if plan.stems_fused else {}),
+                             "quarter": {j: cp.quarter for j, cp in enumerate(plan.cells)}}
         pre: Dict[int, torch.Tensor] = {}
 
         def buf(j):

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -185,6 +185,36 @@ def set_stem_fusion(enabled: bool) -> None:
 
 def stem_fusion_enabled() -> bool:
     return _FUSE_STEMS[0]
+
+
+STORE_QUARTER_ROWS = 2            # store_main bit 1 of ragmi_conv3d_k3_dual_fwd_ex (include/rag_amd.h)
+_QUARTER_STORE = [os.environ.get("RAGMI_QUARTER_STORE", "1") != "0"]      # the DEFAULT, read once at import (A/B tooling)
+
+
+def set_quarter_store(enabled: bool) -> None:
+    """Whether the fused executor may skip the part of a level-3 main store that its only reader — a x0.25 resample two levels down —
+    never touches (RAGMI_STORE_QUARTER_ROWS: 3/4 of the planes x rows).  Same bits either way; for A/B runs and tests."""
+    _QUARTER_STORE[0] = bool(enabled)
+
+
+def quarter_store_enabled() -> bool:
+    return _QUARTER_STORE[0]
+
+
+def quarter_store_supported(cin: int, cout: int, B: int, D: int, H: int, W: int, nset: int = 2, ntail: int = 0, ndown: int = 1,
+                            dtype: torch.dtype = torch.float32) -> bool:
+    """True when this conv3d_k3_dual call (cin = both inputs) takes quarter=True under the current precision setting
+    (ragmi_conv3d_k3_quarter_store_supported)."""
+    return bool(load_library().ragmi_conv3d_k3_quarter_store_supported(cin, cout, B, D, H, W, nset, ntail, ndown, _conv_dt(_DT[dtype])))
+
+
+def quarter_store_rows(n_in: int) -> Optional[List[bool]]:
+    """Which source indices of an axis of n_in voxels a x0.25 trilinear align_corners=True resample reads — the planes / rows a
+    quarter=True launch writes (ragmi_quarter_store_rows); None where the axis does not qualify."""
+    used = (ctypes.c_ubyte * max(int(n_in), 1))()
+    if not load_library().ragmi_quarter_store_rows(int(n_in), used):
+        return None
+    return [bool(v) for v in used]
 
 
 def set_g4(enabled: bool) -> None:
@@ -462,9 +492,13 @@ def conv3d_k3_dual(x: torch.Tensor, cin_a: int, packed_a: torch.Tensor, scale_a,
                    packed_b: torch.Tensor, scale_b, shift_b, cout: int, relu: bool, out: torch.Tensor,
                    out_group_ch: Optional[Sequence[int]] = None, res: Optional[torch.Tensor] = None,
                    res_group_ch: Optional[Sequence[int]] = None, tails: Optional[Sequence[Tail]] = None,
-                   store_main: bool = True, x_g4: bool = False) -> torch.Tensor:
+                   store_main: bool = True, x_g4: bool = False, quarter: bool = False) -> torch.Tensor:
     """Two sibling ConvBR_3d groups in one launch: out = act(bnA(convA(x[:, :cin_a]))) + act(bnB(convB(x[:, cin_a:])))
-    (+ res): see ragmi_conv3d_k3_dual_fwd in include/rag_amd.h.  x_g4: x is stored channel-group-interleaved (RAGMI_CONV_X_G4)."""
+    (+ res): see ragmi_conv3d_k3_dual_fwd in include/rag_amd.h.  x_g4: x is stored channel-group-interleaved (RAGMI_CONV_X_G4).
+    quarter: `out` is read only by a x0.25 align_corners=True resample — the planes and rows that resample never reads stay
+    UNWRITTEN (RAGMI_STORE_QUARTER_ROWS; an error where quarter_store_supported says no)."""
+    if quarter and not store_main:
+        raise ValueError("conv3d_k3_dual: quarter=True qualifies a main store")
     if x_g4 and not x.is_contiguous():
         raise ValueError("conv3d_k3_dual: a G4 input is a contiguous buffer")
     _need_gpu(packed_a, packed_b, scale_a, shift_a, scale_b, shift_b)
@@ -484,7 +518,7 @@ def conv3d_k3_dual(x: torch.Tensor, cin_a: int, packed_a: torch.Tensor, scale_a,
         Cx - cin_a, packed_b.data_ptr(), ptr(scale_b), ptr(shift_b), int(relu) | (CONV_X_G4 if x_g4 else 0),
         out.data_ptr(), _planes(out), _i32_array(out_group_ch),
         ptr(res), _planes(res) if res is not None else 0, _i32_array(res_group_ch),
-        B, cout, D, H, W, int(store_main), ntail, tarr, _conv_dt(dt), _stream()), "conv3d_k3_dual")
+        B, cout, D, H, W, int(store_main) | (STORE_QUARTER_ROWS if quarter else 0), ntail, tarr, _conv_dt(dt), _stream()), "conv3d_k3_dual")
     return out
 
 
