@@ -677,6 +677,42 @@ int ragmi_color_stats(const void* img_u8, int B, int Hs, int Ws, void* workspace
 int ragmi_color_transfer(const void* target_u8, const void* stats_target, const void* stats_source, void* out_u8, int B, int H, int W,
                          void* stream);
 
+/* Lanczos resize on the device, Pillow's arithmetic bit for bit: the Cityscapes branch of the reference's loaders
+ * (src_self/dataloaders/stereo_dataset.py:56-69: left / right / disparity .resize((1024, 512), Image.ANTIALIAS), ANTIALIAS being
+ * Lanczos, before the crop or pad; disparity / 256 / 2).  The taps come from the caller, per axis (y: Hs -> Hr, x: Ws -> Wr), as
+ * Pillow's precompute_coeffs gives them in float64 (rag_amd.data.lanczos_taps), all on the device:
+ *   bounds    int32 [m,2]        (first source index, tap count) per output index
+ *   taps_i32  int32 [m,ksize]    8-bit path: the tap * 2^22 rounded half away from zero, 0 past the tap count
+ *   taps_f64  float64 [m,ksize]  16-bit path: the tap, 0 past the tap count
+ * with ksize = 2 * ceil(3 * max(n/m, 1)) + 1, and for n == m (an axis Pillow does not filter) the identity: bounds (i, 1), one tap
+ * 2^22 / 1.0, ksize 1.  8-bit: clip8((2^21 + sum px * K) >> 22) in int32.  16-bit (I;16): a double from 0.0, acc += px * k in
+ * ascending order with product and sum rounded separately, r = (int)(acc +- 0.5), the bytes clip8(r % 256) and clip8(r >> 8)
+ * clipped separately.  The horizontal pass runs first and is stored as uint8 / uint16 before the vertical one.
+ *
+ * One workgroup resamples one 16x64 output tile from the window of source pixels it needs, staged in LDS; the window is sized on
+ * the host from the sizes alone and every table entry is clamped to it, so a wrong table gives wrong pixels and never an access
+ * out of bounds.  RAGMI_EUNSUPPORTED: a window that does not fit the 160 KiB of LDS (an extreme downscale); nothing is launched.
+ * RAGMI_EINVAL: null / misaligned pointer, non-positive size, a ksize other than the formula's.  One launch each, no allocation,
+ * no host synchronisation, no atomics, no memset or memcpy.
+ *
+ * ragmi_prep_batch_resized: ragmi_prep_batch with the resize in front, still ONE launch and without the resized image in memory
+ * (stereo_dataset.py:56-69 then :73-122).  left_u8, right_u8 [B,Hs,Ws,3] uint8 and gt [B,Hs,Ws] uint16 (gt_dtype must be
+ * RAGMI_GT_U16: the reference resizes PNGs only) are resized to Hr x Wr; origin (device int32 [B,2]) addresses the RESIZED image:
+ * output pixel (y, x) is resized pixel (y + origin[b,0], x + origin[b,1]), 0 outside it (after normalisation); gt_out =
+ * (float)resized * gt_scale (1/512 for the reference's / 256 / 2: exact).  No colour transfer.  ytaps_f64 / xtaps_f64 may be NULL
+ * without a gt. */
+int ragmi_prep_batch_resized(const void* left_u8, const void* right_u8, const void* gt, int gt_dtype, float gt_scale, const void* origin,
+                             void* left, void* right, void* gt_out, int B, int Hs, int Ws, int Hr, int Wr, int H, int W, float mean0,
+                             float mean1, float mean2, float std0, float std1, float std2, const void* ybounds, const void* ytaps_i32,
+                             const void* ytaps_f64, int yksize, const void* xbounds, const void* xtaps_i32, const void* xtaps_f64,
+                             int xksize, void* stream);
+/* The resize alone (stereo_dataset.py:59-61), the same kernel and device functions: [B,Hs,Ws,3] uint8 -> [B,Hr,Wr,3] uint8 (mode
+ * RGB) and [B,Hs,Ws] uint16 -> [B,Hr,Wr] uint16 (mode I;16). */
+int ragmi_resize_lanczos_u8(const void* src_u8, void* dst_u8, int B, int Hs, int Ws, int Hr, int Wr, const void* ybounds,
+                            const void* ytaps_i32, int yksize, const void* xbounds, const void* xtaps_i32, int xksize, void* stream);
+int ragmi_resize_lanczos_u16(const void* src_u16, void* dst_u16, int B, int Hs, int Ws, int Hr, int Wr, const void* ybounds,
+                             const void* ytaps_f64, int yksize, const void* xbounds, const void* xtaps_f64, int xksize, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Host-side guard for captured steps (no device work): counts the nodes of a captured hipGraph_t by kind.  A captured training
  * step must consist of kernel nodes only: on ROCm 7.2 memset / memcpy NODES of an instantiated graph were corrupted by memcpys

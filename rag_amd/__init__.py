@@ -25,11 +25,11 @@ from .supernet import AutoFeature, AutoMatching, BasicNetwork  # noqa: E402,F401
 from . import depth  # noqa: E402,F401
 from .depth import DepthNetwork, load_depth_checkpoint  # noqa: E402,F401
 from . import data  # noqa: E402,F401
-from .data import color_stats, prepare_batch, random_crop_origin, transfer_color  # noqa: E402,F401
+from .data import color_stats, lanczos_taps, prepare_batch, random_crop_origin, resize_lanczos, resize_lanczos_torch, transfer_color  # noqa: E402,F401
 
 __all__ = [
     "Network", "Cell_2d", "ConvBR_2d", "DepthNetwork", "load_depth_checkpoint",
-    "data", "prepare_batch", "random_crop_origin", "color_stats", "transfer_color",
+    "data", "prepare_batch", "random_crop_origin", "color_stats", "transfer_color", "lanczos_taps", "resize_lanczos", "resize_lanczos_torch",
     "ops", "load_library", "lib_path", "MatchingNet", "Cell_3d", "ConvBR_3d", "Identity_3d", "Disp",
     "DisparityRegression", "OPS_3d", "PRIMITIVES_3D", "Genotype", "ALL_CONV_GENOTYPE", "ALL_SKIP_GENOTYPE",
 ]

@@ -17,6 +17,7 @@
 //                  order (strided, then an LDS tree) by one workgroup per sample.  No atomics, no memset.
 //   color_transfer the stand-alone uint8 image of transfer_color (tests, callers that want the image).
 #include "common.h"
+#include "prep_common.h"
 
 namespace ragmi {
 
@@ -38,12 +39,6 @@ __device__ __forceinline__ int transfer_level(int u, double tm, double ts, doubl
   t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
   t = t * 255.0;
   return (t >= 0.0 && t <= 255.0) ? (int)t : 0;        // NaN lands here
-}
-
-__device__ __forceinline__ float normalize_level(int level, float mean, float std) {
-#pragma clang fp contract(off)
-  const float v = (float)level / 255.0f;
-  return (v - mean) / std;
 }
 
 struct PrepArgs {
@@ -281,8 +276,6 @@ __global__ __launch_bounds__(PREP_WG) void color_transfer_kernel(const uint8_t* 
     for (int64_t j = (int64_t)blockIdx.x * PREP_WG + tid; j < n; j += (int64_t)gridDim.x * PREP_WG) po[j] = lut[(int)(j % 3) * 256 + pi[j]];
   }
 }
-
-static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace ragmi
 
