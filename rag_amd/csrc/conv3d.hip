@@ -120,6 +120,56 @@ int fill_tails(K3Args& a, int store_main, int ntail, const ragmi_tail_t* tails, 
   return RAGMI_OK;
 }
 
+K3Route k3_route(const K3Args& a, int nset, int dtype) {
+  if (x2d_eligible(a, nset, dtype)) return K3Route::Split2d;
+  if (x3d_eligible(a, nset, dtype)) return K3Route::Box;
+  if (!x3_eligible(a, nset, dtype)) return K3Route::Mfma;
+#ifndef RAGMI_NO_X3Q      // A/B builds: the level-3 dual cells on the z-marching kernel
+  if (xq_takes(a, nset, dtype)) return K3Route::QuadRing;
+#endif
+  return K3Route::ZMarch;
+}
+
+bool k3_probe(K3Args& a, int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int ndown) {
+  if (Cin <= 0 || Cout <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || (nset != 1 && nset != 2) || (nset == 2 && Cin % (2 * CK))) return false;
+  a = K3Args{};
+  a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.ntail = ntail; a.ndown = ndown;
+  a.res = has_res ? (const void*)&a : nullptr;      // (only ever compared with null)
+  for (int t = 0; t < 2; ++t) a.tail_cout[t] = a.down_cout[t] = 4;
+  for (int g = 0; g < (Cout + 3) / 4 && g < RAGMI_MAX_GROUPS; ++g) a.y_ch[g] = 4 * g;
+  if (nset == 2) a.nchunks[0] = a.nchunks[1] = Cin / (2 * CK);
+  else a.nchunks[0] = (Cin + CK - 1) / CK;
+  a.store_main = 1;
+  return true;
+}
+
+// what the two entry points do once their arguments are marshalled into `a`: the flag checks, the route and its launch
+static int k3_dispatch(const K3Args& a, int nset, int dtype, hipStream_t s) {
+  const char* const who = nset == 2 ? "conv3d_k3_dual" : "conv3d_k3";
+  if (a.store_main & RAGMI_STORE_QUARTER_ROWS)
+    RAGMI_REQUIRE((a.store_main & 1) && x3_quarter_store_ok(a, nset, dtype), RAGMI_EUNSUPPORTED,
+                  "%s: this call does not take RAGMI_STORE_QUARTER_ROWS (ragmi_conv3d_k3_quarter_store_supported)", who);
+  const int want = ((a.relu & RAGMI_CONV_X_G4) ? 1 : 0) | (a.tail_g4 ? 2 : 0);
+  RAGMI_REQUIRE(!(a.relu & RAGMI_CONV_Y_G4), RAGMI_EUNSUPPORTED, "%s: the main output is channel planes (RAGMI_CONV_Y_G4 not built here)", who);
+  RAGMI_REQUIRE((x3_g4_caps(a, nset, dtype) & want) == want, RAGMI_EUNSUPPORTED,
+                "%s: this shape / dtype does not take G4 tensors (ragmi_conv3d_k3_g4_caps)", who);
+  const K3Route route = k3_route(a, nset, dtype);
+  switch (route) {
+    case K3Route::Split2d: return x2d_launch(a, nset, dtype, s);
+    case K3Route::Box: return x3d_launch(a, nset, dtype, s);
+    case K3Route::QuadRing:
+    case K3Route::ZMarch: return x3_launch(a, nset, dtype, route, s);
+    case K3Route::Mfma: break;
+  }
+  RAGMI_REQUIRE(a.ndown == 0, RAGMI_EUNSUPPORTED, "%s: down-sampling tails need the z-marching split-operand form (ragmi_conv3d_k3_uses_x3)", who);
+  using Launch = int (*)(const K3Args&, int, hipStream_t);
+  static const Launch mfma[2][3][2] = {      // [set count - 1][choose_cfg][bf16 storage]
+      {{launch_k3_s1_cfg0_f32, launch_k3_s1_cfg0_bf16}, {launch_k3_s1_cfg1_f32, launch_k3_s1_cfg1_bf16}, {launch_k3_s1_cfg2_f32, launch_k3_s1_cfg2_bf16}},
+      {{launch_k3_s2_cfg0_f32, launch_k3_s2_cfg0_bf16}, {launch_k3_s2_cfg1_f32, launch_k3_s2_cfg1_bf16}, {launch_k3_s2_cfg2_f32, launch_k3_s2_cfg2_bf16}}};
+  const int cfg = choose_cfg(a.B, a.D, a.H, a.W, a.Cout);
+  return mfma[nset - 1][cfg == 0 || cfg == 1 ? cfg : 2][dtype == RAGMI_BF16](a, (a.Cout + 3) / 4, s);
+}
+
 }  // namespace ragmi
 
 // packed weights = [fp32-MFMA section: groups x chunks x PACK_PER_GC floats][bf16x3 fragments of conv3d_x3.hip]
@@ -181,24 +231,7 @@ extern "C" int ragmi_conv3d_k3_fwd_ex(const void* x, int64_t x_bstride, const vo
   a.nchunks[0] = (Cin + CK - 1) / CK;
   const int rt = fill_tails(a, store_main, ntail, tails, Cout);
   if (rt != RAGMI_OK) return rt;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int ng = (Cout + 3) / 4;
-  const bool bf = dtype == RAGMI_BF16;
-  {
-    const int want = ((relu & RAGMI_CONV_X_G4) ? 1 : 0) | (a.tail_g4 ? 2 : 0);
-    RAGMI_REQUIRE(!(relu & RAGMI_CONV_Y_G4), RAGMI_EUNSUPPORTED, "conv3d_k3: the main output is channel planes (RAGMI_CONV_Y_G4 not built here)");
-    RAGMI_REQUIRE((x3_g4_caps(a, 1, dtype) & want) == want, RAGMI_EUNSUPPORTED,
-                  "conv3d_k3: this shape / dtype does not take G4 tensors (ragmi_conv3d_k3_g4_caps)");
-  }
-  if (x2d_eligible(a, 1, dtype)) return x2d_launch(a, 1, dtype, s);
-  if (x3d_eligible(a, 1, dtype)) return x3d_launch(a, 1, dtype, s);
-  if (x3_eligible(a, 1, dtype)) return x3_launch(a, 1, dtype, s);
-  RAGMI_REQUIRE(a.ndown == 0, RAGMI_EUNSUPPORTED, "conv3d_k3: down-sampling tails need the z-marching split-operand form (ragmi_conv3d_k3_uses_x3)");
-  switch (choose_cfg(B, D, H, W, Cout)) {
-    case 0: return bf ? launch_k3_s1_cfg0_bf16(a, ng, s) : launch_k3_s1_cfg0_f32(a, ng, s);
-    case 1: return bf ? launch_k3_s1_cfg1_bf16(a, ng, s) : launch_k3_s1_cfg1_f32(a, ng, s);
-    default: return bf ? launch_k3_s1_cfg2_bf16(a, ng, s) : launch_k3_s1_cfg2_f32(a, ng, s);
-  }
+  return k3_dispatch(a, 1, dtype, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ragmi_conv3d_k3_small_fwd(const void* x, int64_t x_bstride, const void* weight, const void* scale,
@@ -267,29 +300,9 @@ extern "C" int ragmi_conv3d_k3_dual_fwd_ex(const void* x, int64_t x_bstride, int
   a.nchunks[1] = (CinB + CK - 1) / CK;
   const int rt = fill_tails(a, store_main, ntail, tails, Cout);
   if (rt != RAGMI_OK) return rt;
-  if (store_main & RAGMI_STORE_QUARTER_ROWS) {      // (fill_tails keeps bit 0 only: no other entry point takes the flag)
-    RAGMI_REQUIRE((store_main & 1) && x3_quarter_store_ok(a, 2, dtype), RAGMI_EUNSUPPORTED,
-                  "conv3d_k3_dual: this call does not take RAGMI_STORE_QUARTER_ROWS (ragmi_conv3d_k3_quarter_store_supported)");
-    a.store_main |= RAGMI_STORE_QUARTER_ROWS;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int ng = (Cout + 3) / 4;
-  const bool bf = dtype == RAGMI_BF16;
-  {
-    const int want = ((relu & RAGMI_CONV_X_G4) ? 1 : 0) | (a.tail_g4 ? 2 : 0);
-    RAGMI_REQUIRE(!(relu & RAGMI_CONV_Y_G4), RAGMI_EUNSUPPORTED, "conv3d_k3_dual: the main output is channel planes (RAGMI_CONV_Y_G4 not built here)");
-    RAGMI_REQUIRE((x3_g4_caps(a, 2, dtype) & want) == want, RAGMI_EUNSUPPORTED,
-                  "conv3d_k3_dual: this shape / dtype does not take G4 tensors (ragmi_conv3d_k3_g4_caps)");
-  }
-  if (x2d_eligible(a, 2, dtype)) return x2d_launch(a, 2, dtype, s);
-  if (x3d_eligible(a, 2, dtype)) return x3d_launch(a, 2, dtype, s);
-  if (x3_eligible(a, 2, dtype)) return x3_launch(a, 2, dtype, s);
-  RAGMI_REQUIRE(a.ndown == 0, RAGMI_EUNSUPPORTED, "conv3d_k3_dual: down-sampling tails need the z-marching split-operand form (ragmi_conv3d_k3_uses_x3)");
-  switch (choose_cfg(B, D, H, W, Cout)) {
-    case 0: return bf ? launch_k3_s2_cfg0_bf16(a, ng, s) : launch_k3_s2_cfg0_f32(a, ng, s);
-    case 1: return bf ? launch_k3_s2_cfg1_bf16(a, ng, s) : launch_k3_s2_cfg1_f32(a, ng, s);
-    default: return bf ? launch_k3_s2_cfg2_bf16(a, ng, s) : launch_k3_s2_cfg2_f32(a, ng, s);
-  }
+  // (fill_tails keeps bit 0 only: no other entry point takes the flag; k3_dispatch refuses it without bit 0 or on another launch)
+  if (store_main & RAGMI_STORE_QUARTER_ROWS) a.store_main = (store_main & 1) | RAGMI_STORE_QUARTER_ROWS;
+  return k3_dispatch(a, 2, dtype, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ragmi_down2_tail_supported(int D, int H, int W) {
@@ -297,40 +310,18 @@ extern "C" int ragmi_down2_tail_supported(int D, int H, int W) {
 }
 
 extern "C" int ragmi_conv3d_k3_uses_x3(int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int dtype) {
-  using namespace ragmi;
-  if (Cin <= 0 || Cout <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || (nset != 1 && nset != 2)) return 0;
-  K3Args a{};
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.ntail = ntail;
-  a.res = has_res ? (const void*)&a : nullptr;
-  if (nset == 2) { if (Cin % (2 * CK)) return 0; a.nchunks[0] = a.nchunks[1] = Cin / (2 * CK); }
-  else a.nchunks[0] = (Cin + CK - 1) / CK;
-  a.store_main = 1;
-  return (x2d_eligible(a, nset, dtype) || x3d_eligible(a, nset, dtype) || x3_eligible(a, nset, dtype)) ? 1 : 0;
+  ragmi::K3Args a;
+  return (ragmi::k3_probe(a, Cin, Cout, B, D, H, W, nset, has_res, ntail, 0) && ragmi::k3_route(a, nset, dtype) != ragmi::K3Route::Mfma) ? 1 : 0;
 }
 
 extern "C" int ragmi_conv3d_k3_g4_caps(int Cin, int Cout, int B, int D, int H, int W, int nset, int ntail, int ndown, int dtype) {
-  using namespace ragmi;
-  if (Cin <= 0 || Cout <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || (nset != 1 && nset != 2)) return 0;
-  K3Args a{};
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.ntail = ntail; a.ndown = ndown;
-  for (int t = 0; t < 2; ++t) a.tail_cout[t] = a.down_cout[t] = 4;
-  for (int g = 0; g < (Cout + 3) / 4 && g < RAGMI_MAX_GROUPS; ++g) a.y_ch[g] = 4 * g;
-  if (nset == 2) { if (Cin % (2 * CK)) return 0; a.nchunks[0] = a.nchunks[1] = Cin / (2 * CK); }
-  else a.nchunks[0] = (Cin + CK - 1) / CK;
-  a.store_main = 1;
-  return x3_g4_caps(a, nset, dtype);
+  ragmi::K3Args a;
+  return ragmi::k3_probe(a, Cin, Cout, B, D, H, W, nset, 0, ntail, ndown) ? ragmi::x3_g4_caps(a, nset, dtype) : 0;
 }
 
 extern "C" int ragmi_conv3d_k3_quarter_store_supported(int Cin, int Cout, int B, int D, int H, int W, int nset, int ntail, int ndown, int dtype) {
-  using namespace ragmi;
-  if (Cin <= 0 || Cout <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || nset != 2 || Cin % (2 * CK)) return 0;
-  K3Args a{};
-  a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.ntail = ntail; a.ndown = ndown;
-  for (int t = 0; t < 2; ++t) a.tail_cout[t] = a.down_cout[t] = 4;
-  for (int g = 0; g < (Cout + 3) / 4 && g < RAGMI_MAX_GROUPS; ++g) a.y_ch[g] = 4 * g;
-  a.nchunks[0] = a.nchunks[1] = Cin / (2 * CK);
-  a.store_main = 1;
-  return x3_quarter_store_ok(a, nset, dtype) ? 1 : 0;
+  ragmi::K3Args a;
+  return (nset == 2 && ragmi::k3_probe(a, Cin, Cout, B, D, H, W, nset, 0, ntail, ndown) && ragmi::x3_quarter_store_ok(a, nset, dtype)) ? 1 : 0;
 }
 
 extern "C" int ragmi_quarter_store_rows(int n_in, unsigned char* used) {

@@ -624,21 +624,32 @@ int64_t x3_packed_words(int Cout, int Cin);
 bool c1_eligible(const K3Args& a, int dtype, int y_dtype);
 int c1_launch(const K3Args& k, int dtype, int y_dtype, hipStream_t st);
 int pack_both(const float* w, float* packed, int64_t total_k3, int Cout, int Cin, int transpose, int planar, bool all, hipStream_t s);
+// Which kernel a 3x3x3 call runs on, in order of precedence: the depth-1 split-operand kernel (conv2d_x3.hip), the deep-level box kernel
+// (conv3d_x3d_kernel), the z-marching work list on the quad-ring kernel (conv3d_x3q.hip) or on conv3d_x3_kernel, else the fp32-MFMA
+// conv3d_k3_kernel.  k3_route (conv3d.hip) alone decides: entry points, predicates and the fused stem ask it, so what a predicate promises
+// is what the launch does.  The four shape conditions below it say what each split-operand kernel serves; only k3_route calls them.
+enum class K3Route { Split2d, Box, QuadRing, ZMarch, Mfma };
+K3Route k3_route(const K3Args& a, int nset, int dtype);
+bool x2d_eligible(const K3Args& a, int nset, int dtype);
+bool x3d_eligible(const K3Args& a, int nset, int dtype);
 bool x3_eligible(const K3Args& a, int nset, int dtype);
+bool xq_takes(const K3Args& a, int nset, int dtype);
+// a synthetic launch of this shape for the predicates: every field a shape condition reads, filled as the entry points fill it for
+// 4-channel tails and output groups in order.  false: a non-positive size, nset not 1 or 2, or two sets that are not whole equal chunks
+bool k3_probe(K3Args& a, int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int ndown);
 int x3_g4_caps(const K3Args& a, int nset, int dtype);      // G4 forms (include/rag_amd.h) the kernel this call lands on takes
 bool x3_quarter_store_ok(K3Args a, int nset, int dtype);      // RAGMI_STORE_QUARTER_ROWS (include/rag_amd.h): the launch this call lands on takes it
 bool quarter_store_rows(int n_in, unsigned char* used);       // the source indices a x0.25 align_corners=True resample reads on one axis
 struct X3StemSrc;
-int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* src = nullptr);
+// route: K3Route::ZMarch or K3Route::QuadRing, as k3_route answered (a plane source runs on ZMarch)
+int x3_launch(K3Args a, int nset, int dtype, K3Route route, hipStream_t st, const X3StemSrc* src = nullptr);
 // argument marshalling of the 3x3x3 entry points (conv3d.hip), shared with ragmi_costvol_stem_conv3d_fwd (costvol_stem.hip)
 int fill_common(K3Args& a, const void* x, int64_t x_bstride, void* y, int64_t y_bstride, const int32_t* y_group_ch, const void* res,
                 int64_t res_bstride, const int32_t* res_group_ch, int B, int Cin, int Cout, int D, int H, int W, int relu);
 int fill_tails(K3Args& a, int store_main, int ntail, const ragmi_tail_t* tails, int Cout);
 // deep-level bf16x3 form (8 / 16 input channels per set, box tiles): levels 6 and 12
 // depth-1 volumes (the Feature Net's 2-D convolutions) on the split-operand form: conv2d_x3.hip
-bool x2d_eligible(const K3Args& a, int nset, int dtype);
 int x2d_launch(K3Args a, int nset, int dtype, hipStream_t st);
-bool x3d_eligible(const K3Args& a, int nset, int dtype);
 int x3d_launch(K3Args a, int nset, int dtype, hipStream_t st);
 int launch_k3_valu_f32(const K3Args& a, int cfg, hipStream_t s);          // Cout <= 2, raw weights
 int launch_k3_valu_bf16(const K3Args& a, int cfg, hipStream_t s);

@@ -1132,10 +1132,9 @@ bool x3_eligible(const K3Args& a, int nset, int dtype) {
 
 // which G4 forms (include/rag_amd.h) the kernel this call lands on takes: bit 0 a G4 input, bit 1 G4 full-resolution tails
 int x3_g4_caps(const K3Args& a, int nset, int dtype) {
-  if ((dtype != RAGMI_F32X3 && dtype != RAGMI_BF16) || x2d_eligible(a, nset, dtype) || x3d_eligible(a, nset, dtype) || !x3_eligible(a, nset, dtype)) return 0;
-#ifndef RAGMI_NO_X3Q
-  if (xq_takes(a, nset, dtype)) return 3;
-#endif
+  const K3Route route = k3_route(a, nset, dtype);
+  if (route == K3Route::QuadRing) return 3;
+  if (route != K3Route::ZMarch) return 0;
   const int ncg = a.nchunks[0] + (nset == 2 ? a.nchunks[1] : 0);
   // a G4 input: stem3d1's shape (12 channels, one set) in either storage type; under bf16 storage also the level-3 dual cells (4 + 4
   // channels — fp32 storage runs those on conv3d_x3q_kernel, above)
@@ -1249,11 +1248,7 @@ constexpr int XQ_QMAX = 256;      // planes / rows the launch's bit tables hold 
 // a multiple of 4 planes (the half items included) and at most 32 planes long (one 32-bit plane mask per item)
 bool x3_quarter_store_ok(K3Args a, int nset, int dtype) {
   if (dtype != RAGMI_F32X3 || nset != 2 || a.Cout != 12 || a.ndown == 0 || a.ntail != 0 || !a.store_main) return false;
-  if (x2d_eligible(a, nset, dtype) || x3d_eligible(a, nset, dtype) || !x3_eligible(a, nset, dtype)) return false;
-#ifdef RAGMI_NO_X3Q
-  return false;
-#endif
-  if (!xq_takes(a, nset, dtype)) return false;
+  if (k3_route(a, nset, dtype) != K3Route::QuadRing) return false;
   if (a.D % 4 || a.H % 4 || a.W % 4 || a.D > XQ_QMAX || a.H > XQ_QMAX) return false;
   if (!quarter_store_rows(a.D, nullptr) || !quarter_store_rows(a.H, nullptr) || !quarter_store_rows(a.W, nullptr)) return false;
   X3Extra e{};
@@ -1266,7 +1261,7 @@ bool x3_quarter_store_ok(K3Args a, int nset, int dtype) {
 }
 
 // a: as filled for the fp32 kernel (wp[s] = packed weights: fp32-MFMA section followed by the bf16x3 fragments)
-int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* src) {
+int x3_launch(K3Args a, int nset, int dtype, K3Route route, hipStream_t st, const X3StemSrc* src) {
 #ifdef RAGMI_DIAG
   static const int diag_x3 = [] { const char* v = getenv("RAGMI_X3_DIAG"); return v ? atoi(v) : 0; }();   // 1 no stores, 2 no MFMA block, 4 no commit, 8 no loads, 16 operand reads at one address, 32 in-kernel stamps, 64 / 128 (quad-ring kernel) no finishing step / no parking of the down-sampling tails
   a.relu |= diag_x3 << 8;
@@ -1280,7 +1275,8 @@ int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* sr
   const int ncog = (a.Cout + 15) / 16;
   x3_schedule(a, dtype, ncog, e);
   if (a.store_main & RAGMI_STORE_QUARTER_ROWS) {
-    RAGMI_REQUIRE(!src && x3_quarter_store_ok(a, nset, dtype), RAGMI_EUNSUPPORTED,
+    // (the entry point asked x3_quarter_store_ok; here only what the bit tables below rest on)
+    RAGMI_REQUIRE(route == K3Route::QuadRing && a.D <= XQ_QMAX && a.H <= XQ_QMAX, RAGMI_EUNSUPPORTED,
                   "conv3d_x3: this launch does not take RAGMI_STORE_QUARTER_ROWS (ragmi_conv3d_k3_quarter_store_supported)");
     unsigned char used[XQ_QMAX];
     quarter_store_rows(a.D, used);
@@ -1298,9 +1294,7 @@ int x3_launch(K3Args a, int nset, int dtype, hipStream_t st, const X3StemSrc* sr
                      (a.ndown > 0 ? (size_t)(2 * 2 * 4 * X3_TY * (X3_TX / 2)) * sizeof(float) + (size_t)(X3_TX / 2 + X3_TY / 2) * sizeof(float4) : 0);
   RAGMI_REQUIRE(lds <= 160 * 1024, RAGMI_EUNSUPPORTED, "conv3d_x3: tile does not fit the LDS");
   const dim3 grid((unsigned)std::min<int64_t>(nwork, 1 << 20), ncog);      // x is cut to the resident slots where the kernel is known
-#ifndef RAGMI_NO_X3Q
-  if (!src && xq_takes(a, nset, dtype)) return xq_launch(a, e, nset, grid, st);     // one 4-channel group per set, fp32 storage: conv3d_x3q.hip
-#endif
+  if (route == K3Route::QuadRing) return xq_launch(a, e, nset, grid, st);     // one 4-channel group per set, fp32 storage: conv3d_x3q.hip
   if (nset == 2) {
     switch (ncg) {
       case 2: return x3_launch_one<2, 2>(a, e, grid, lds, st);

@@ -598,7 +598,7 @@ size_t xq_lds_bytes(int nset, bool down) {
          (down ? (size_t)(XQ_DU_SLOTS * XQ_DU_PLANE) * sizeof(float) + (size_t)(X3_TX / 2 + X3_TY / 2) * sizeof(float4) : 0);
 }
 
-// the shapes conv3d_x3_kernel<float, NSET, NSET, *> serves (x3_launch decides eligibility and the work list)
+// the shapes conv3d_x3q_kernel serves among those x3_eligible takes (k3_route asks; x3_launch makes the work list)
 bool xq_takes(const K3Args& a, int nset, int dtype) {
   const int64_t vol = (int64_t)a.D * a.H * a.W;
   int ych = 0;                                     // buffer addressing: every byte offset inside a sample below 2^31

@@ -582,7 +582,7 @@ extern "C" int ragmi_costvol_stem_conv3d_fwd(const void* left, const void* right
   a.nchunks[0] = (Cmid + CK - 1) / CK;
   rc = fill_tails(a, store_main, ntail, tails, Cout);
   if (rc != RAGMI_OK) return rc;
-  RAGMI_REQUIRE(a.ndown == 0 && x3_eligible(a, 1, dtype) && !x3d_eligible(a, 1, dtype) && !x2d_eligible(a, 1, dtype), RAGMI_EUNSUPPORTED,
+  RAGMI_REQUIRE(a.ndown == 0 && k3_route(a, 1, dtype) == K3Route::ZMarch, RAGMI_EUNSUPPORTED,
                 "costvol_stem_conv3d: this shape does not run on the z-marching split-operand kernel (ragmi_costvol_stem_conv3d_supported)");
   // ONE fused tail of stem3d0 (4 output channels, full resolution: cell 0's pre_preprocess) can ride in rows 12..15 of stem3d1's matrix
   // product (RAGMI_TAIL_ROWS: the caller packed it there) — no combine launch at all; any other tail goes through the combine kernel
@@ -610,15 +610,14 @@ extern "C" int ragmi_costvol_stem_conv3d_fwd(const void* left, const void* right
   }
   src.wband = l.wband; src.wb1 = l.wb1; src.u1_0 = l.u1_0;
   src.scale = (const float*)scale0; src.shift = (const float*)shift0; src.relu = relu0 & 1;
-  return x3_launch(a, 1, dtype, static_cast<hipStream_t>(stream), &src);
+  return x3_launch(a, 1, dtype, K3Route::ZMarch, static_cast<hipStream_t>(stream), &src);
 }
 
 extern "C" int ragmi_costvol_stem_conv3d_supported(int C, int Cmid, int Cout, int B, int D, int H, int W, int ntail, int dtype) {
   using namespace ragmi;
-  if ((dtype != RAGMI_F32X3 && dtype != RAGMI_BF16) || Cmid != 12 || C % 4 != 0 || C <= 0 || C > 12 || Cout <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  K3Args a{};
-  a.B = B; a.Cin = Cmid; a.Cout = Cout; a.D = D; a.H = H; a.W = W; a.ntail = ntail; a.nchunks[0] = Cmid / CK; a.store_main = 1;
-  return (x3_eligible(a, 1, dtype) && !x3d_eligible(a, 1, dtype) && !x2d_eligible(a, 1, dtype)) ? 1 : 0;
+  if ((dtype != RAGMI_F32X3 && dtype != RAGMI_BF16) || Cmid != 12 || C % 4 != 0 || C <= 0 || C > 12) return 0;
+  K3Args a;
+  return (k3_probe(a, Cmid, Cout, B, D, H, W, 1, 0, ntail, 0) && k3_route(a, 1, dtype) == K3Route::ZMarch) ? 1 : 0;
 }
 
 static int stem_run(const void* left, const void* right, const void* variants, const void* scale, const void* shift,

@@ -455,3 +455,60 @@ def test_chain_plan_dual_cells_by_genotype(built_lib, rows, any_dual, dtype):
                 assert cp.store_main or cp.tails      # a concat nobody stores went to tails
     finally:
         _switches(ops)
+
+
+# ---- which kernel a 3x3x3 call runs on is decided once in the library (k3_route, rag_amd/csrc/conv3d.hip); the four shape predicates
+# the fused executor plans from all ask it, so their answers cannot contradict each other.
+def _csrc_constant(name):
+    for fn in ("conv3d_x3_common.h", "conv3d_x3.hip"):
+        m = re.search(r"constexpr int64_t %s = 1 << (\d+);" % name, open(os.path.join(ROOT, "rag_amd", "csrc", fn)).read())
+        if m:
+            return 1 << int(m.group(1))
+    raise AssertionError(name)
+
+
+def _k3_shape_grid():
+    """(D, H, W): depth 1 and 2, W on both sides of every kernel's minimum, D = 7 / 8 around the z-marching minimum, volumes one row
+    below and exactly at the two voxel thresholds, and the two level-3 volumes of the chain-plan tests above."""
+    shapes = [(1, 64, W) for W in (8, 16, 31, 32)]
+    for thr in (_csrc_constant("XD_MIN_VOXELS"), _csrc_constant("X3_MIN_VOXELS")):
+        for D in (2, 7, 8):
+            for W in (8, 16, 31, 32):
+                at = -(-thr // (D * W))
+                shapes += [(D, at - 1, W), (D, at, W)]
+    return shapes + [(32, 64, 128), (64, 128, 416)]
+
+
+@pytest.mark.parametrize("shape", _k3_shape_grid(), ids=lambda s: "x".join(map(str, s)))
+def test_k3_host_predicates_agree(built_lib, shape):
+    from rag_amd import ops
+    uses_x3, g4_caps = built_lib.ragmi_conv3d_k3_uses_x3, built_lib.ragmi_conv3d_k3_g4_caps
+    quarter, stem = built_lib.ragmi_conv3d_k3_quarter_store_supported, built_lib.ragmi_costvol_stem_conv3d_supported
+    B, (D, H, W) = 2, shape
+    fired = set()
+    for dt in (ops.F32, ops.BF16, ops.F32X3):
+        for cps in (4, 8, 12, 16, 24):
+            for nset in (1, 2):
+                for cout in (12, 16, 20):
+                    for ntail in range(3):
+                        vol = (cps * nset, cout, B, D, H, W, nset)
+                        u = uses_x3(*vol, 0, ntail, dt)
+                        fired.update(["x3"] if u else [])
+                        for ndown in range(3):
+                            caps, q = g4_caps(*vol, ntail, ndown, dt), quarter(*vol, ntail, ndown, dt)
+                            fired.update((["caps"] if caps else []) + (["quarter"] if q else []))
+                            assert 0 <= caps <= 3 and q in (0, 1)
+                            assert not q or caps == 3, (vol, ntail, ndown, dt)
+                            assert not caps or u, (vol, ntail, ndown, dt)
+                            assert dt != ops.F32 or not (u or caps or q), (vol, ntail, ndown, dt)
+        for C in (4, 8, 12):
+            for cout in (12, 16, 20):
+                for ntail in range(3):
+                    s = stem(C, 12, cout, B, D, H, W, ntail, dt)
+                    fired.update(["stem"] if s else [])
+                    assert not s or (dt != ops.F32 and uses_x3(12, cout, B, D, H, W, 1, 0, ntail, dt)), (C, cout, shape, ntail, dt)
+    # the implications are not vacuous: the level-3 volumes take every form, the depth-1 and deep-level ones the split-operand kernels
+    if shape in ((32, 64, 128), (64, 128, 416)):
+        assert fired == {"x3", "caps", "quarter", "stem"}, fired
+    if shape in ((1, 64, 16), (1, 64, 32), (2, 256, 32), (8, 64, 32)):
+        assert fired == {"x3"}, fired
