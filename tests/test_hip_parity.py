@@ -70,9 +70,10 @@ def test_disp_golden(ra):
 
 @pytest.mark.parametrize("B,d,h,w,maxdisp,scale", [(2, 16, 6, 10, 48, 1.0), (1, 64, 8, 12, 192, 5.0), (1, 7, 5, 3, 21, 20.0),
                                                    (1, 9, 4, 6, 20, 1.0),
-                                                   # d = 64, maxdisp = 192 runs the register form (disp.hip disp_softargmin_x3_kernel):
-                                                   # costs of the trained net's magnitude, a peaky softmin, and the generic kernel
-                                                   # on the same d for a ratio that is not 3
+                                                   # every maxdisp == 3 d row, the ones above included, runs the tiled kernel
+                                                   # (disp.hip disp_softargmin_x3_kernel); d = 64, maxdisp = 192 runs its register
+                                                   # form: costs of the trained net's magnitude, a peaky softmin, and the generic
+                                                   # kernel on the same d for a ratio that is not 3
                                                    (1, 64, 20, 33, 192, 1000.0), (2, 64, 6, 9, 192, 1e4), (1, 64, 5, 7, 160, 5.0)])
 def test_disp_vs_oracle(ra, B, d, h, w, maxdisp, scale):
     x = torch.randn((B, 1, d, h, w), generator=gen(5)) * scale   # large scale -> peaky softmin, exercises the online rescale
