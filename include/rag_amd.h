@@ -167,7 +167,7 @@ int ragmi_down2_tail_supported(int D, int H, int W);
  *   dtype RAGMI_BF16 | RAGMI_OUT_F32 of ragmi_conv3d_k1_resample_fwd: x is bf16, y is fp32 (same arithmetic: fp32 on chip). */
 #define RAGMI_TAIL_F32 8
 /* ragmi_costvol_stem_conv3d_fwd only, tails0[0].relu bit 4 (RAGMI_TAIL_ROWS): this tail (4 output channels on stem3d0's 12) is NOT evaluated
- * from `weight` by the staging thread but falls out of stem3d1's matrix product: the caller packed stem3d1's weight as a SIXTEEN-channel
+ * from `weight` by the combine kernel but falls out of stem3d1's matrix product: the caller packed stem3d1's weight as a SIXTEEN-channel
  * convolution whose rows 12..15 hold the tail's weights at the centre tap (zero elsewhere) — rows the 12-channel product leaves idle.  Cout
  * stays 12; the tail's scale / shift / relu / y are used as ever, its products are split-operand ones like the convolution's (the
  * RAGMI_F32X3 bound) instead of an exact fp32 chain. */

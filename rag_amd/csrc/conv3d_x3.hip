@@ -25,16 +25,8 @@
 namespace ragmi {
 
 #ifdef RAGMI_DIAG
-// In-kernel stamps of the z-marching kernel (profiling builds only, RAGMI_X3_DIAG bit 32): per wave the shader cycles (s_memtime) spent in
-// each phase of its plane steps, summed over the launch, plus the wave's first / last s_memtime and s_memrealtime (100 MHz): the clock
-// the chip actually held is d(memtime) / d(memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS item 6).  The values go to a buffer of
-// their own (ragmi_diag_x3_stamp_buffer) that no kernel reads; nothing is computed from them.
+// profiling builds: where the in-kernel stamps of the z-marching kernel go (X3_DIAG_DECODE, conv3d_x3_common.h)
 __device__ unsigned long long* x3_stamp_buf = nullptr;
-constexpr int X3_STAMP_WORDS = 16;
-#define X3_STAMP(k) do { if (dg_stamp) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-                                         dg_sum[k] += t_ - dg_last; dg_last = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-#define X3_STAMP(k) do { } while (0)
 #endif
 
 // NCG = input-channel groups of 4 over all sets, NSET accumulator sets (2: out = act(bnA(convA(x[:, :C]))) + act(bnB(convB(x[:, C:]))),
@@ -68,15 +60,12 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
   // plus ~8 instructions of mod-3 arithmetic)
   uint4* const ltail = lw + NSL * 2 * 64;             // fused-tail weight fragments ta1 | ta2 | ta3, [3][64 lanes] (kept out of the registers)
   int2* const loff = reinterpret_cast<int2*>(ltail + 3 * 64);
-  // scale[2][16] (fp32 storage: times the column's 2^e, rewritten per column) | shift[2][16] | tail scale[4 kb][4] | tail shift[4][4] |
-  // static scale[2][16] (BatchNorm scale x the weights' 2^-k) | the column's running max |x| (float bits)
+  // parameter block, lmaxp[2] (one word of overflow notes), down staging (two plane copies, by plane parity): conv3d_x3_common.h
   float* const par = reinterpret_cast<float*>(loff + 3 * NSL * 4);
   unsigned* const lmaxp = reinterpret_cast<unsigned*>(par + 128);
-  // down-sampling tails (TAILS == 2): x-blended tail values of two consecutive planes U[plane parity][down slot 2][8 rows][16][4 ch] |
-  // x table [16]{w0, w1: weights of the source pair (2X, 2X+1)} | y table [4]{...}
   float* const ldu = par + 132;
   float4* const lsrc = reinterpret_cast<float4*>(par + 132);      // XSRC == 2 (no down-sampling tails there): stem3d0's scale[NCG] | shift[NCG] per channel group
-  float4* const ldxt = reinterpret_cast<float4*>(ldu + 2 * 2 * 4 * X3_TY * (X3_TX / 2));
+  float4* const ldxt = reinterpret_cast<float4*>(ldu + 2 * X3_DU_PLANE);
   float4* const ldyt = ldxt + X3_TX / 2;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, kb = lane >> 4;
   const int cog = blockIdx.y;
@@ -87,15 +76,7 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
   }
   asm volatile("" : "+v"(act_floor));      // opaque: otherwise the compiler turns max(u, floor) back into max(u, 0) + a select per value
   const int64_t DHW = (int64_t)HW * a.D;
-#ifdef RAGMI_DIAG
-  const bool dg_nostore = (a.relu & 0x100) != 0, dg_nomfma = (a.relu & 0x200) != 0, dg_nocommit = (a.relu & 0x400) != 0, dg_noload = (a.relu & 0x800) != 0, dg_noread = (a.relu & 0x1000) != 0;
-  const bool dg_stamp = (a.relu & 0x2000) != 0 && x3_stamp_buf != nullptr;
-  unsigned long long dg_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dg_last = 0, dg_t0 = 0, dg_r0 = 0;
-  unsigned dg_steps = 0;
-  if (dg_stamp) { dg_t0 = dg_last = __builtin_amdgcn_s_memtime(); dg_r0 = __builtin_amdgcn_s_memrealtime(); }
-#else
-  constexpr bool dg_nostore = false, dg_nomfma = false, dg_nocommit = false, dg_noload = false, dg_noread = false;
-#endif
+  X3_DIAG_DECODE(a.relu, x3_stamp_buf);
   // weight fragments, 8 bytes (one pair's four channels) at a time: lane quarter q of slice s holds the pairs x3_pair_perm(.., 2q + j)
   // of the packed slice (packed: quarter p >> 1, half p & 1)
   // (every descriptor array of the kernel arguments below is indexed by a COMPILE-TIME index in an unrolled loop, the lanes pick by
@@ -175,55 +156,7 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
       lsrc[tid] = pp ? make_float4(pp[4 * cg], pp[4 * cg + 1], pp[4 * cg + 2], pp[4 * cg + 3]) : make_float4(idv, idv, idv, idv);
     }
   }
-  // Fused consumer 1x1x1 convs ("tails") on the matrix cores: out_t[k][voxel] = sum_c W_t[k][c] * v[c][voxel] as four 16x16x4 fp32
-  // products laid out so that every lane quarter feeds ITS OWN four channels (product r: channel 4 kb + r of each quarter), so no
-  // value crosses lanes.  Rows: tail 0 -> 0..3, tail 1 -> 4..7, down-sampling tails after them.
-  // (TAILS is compile time; the tail fragments and parameters live in LDS and are fetched in the epilogue — in registers they cost
-  // ~20 VGPRs of a 128-VGPR budget and the main loop spilled)
-  if constexpr (TAILS) {
-    // (round 4: the tail products run on v_mfma_f32_16x16x4_f32 — four EXACT fp32 products, product r taking channel 4 kb + r of
-    // every lane quarter — instead of three bf16 products of three-way split operands: the splits were ~28 vector instructions per
-    // tile in a kernel bound by vector issue; the fp32 MFMA holds the issue port for 8 of its 32 cycles)
-    if (tid < 64) {
-      const int row = n, tl = row >> 2, k = row & 3;     // n = lane & 15 is the A row: tail slot tl, its output channel k
-      float wv[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float* const pw = a.tail_w[t];
-        if (t < a.ntail && tl == t && k < a.tail_cout[t]) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { const int c = cog * 16 + 4 * kb + j; if (c < a.Cout) wv[j] = pw[k * a.Cout + c]; }
-        }
-        if constexpr (TAILS == 2) {
-          const float* const pd = a.down_w[t];
-          if (t < a.ndown && tl == a.ntail + t && k < a.down_cout[t]) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const int c = cog * 16 + 4 * kb + j; if (c < a.Cout) wv[j] = pd[k * a.Cout + c]; }
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) reinterpret_cast<float*>(ltail)[j * 64 + lane] = wv[j];
-    }
-    // this lane's tail outputs after that product: rows 4 kb + r -> tail kb, output r
-    if (tid < 16) {
-      const int tk = tid >> 2, r = tid & 3;
-      float sc = 1.f, sh = 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float* const psc = a.tail_scale[t];
-        const float* const psh = a.tail_shift[t];
-        if (t < a.ntail && tk == t && r < a.tail_cout[t] && psc) { sc = psc[r]; sh = psh[r]; }
-        if constexpr (TAILS == 2) {
-          const float* const dsc = a.down_scale[t];
-          const float* const dsh = a.down_shift[t];
-          if (t < a.ndown && tk == a.ntail + t && r < a.down_cout[t] && dsc) { sc = dsc[r]; sh = dsh[r]; }
-        }
-      }
-      par[64 + tid] = sc;
-      par[80 + tid] = sh;
-    }
-  }
+  if constexpr (TAILS) x3_tail_params<TAILS>(a, reinterpret_cast<float*>(ltail), par, cog, tid);      // fused consumer 1x1x1 convs ("tails")
   // staging elements of a thread: (channel group, halo voxel) pairs numbered p * X3_THREADS + tid through the groups — or, with the
   // plane source (XSRC == 2, three groups), TWO elements per thread that share as much of the plane addressing as possible: thread
   // t < 340 stages groups 0 and 1 of halo voxel t (one address computation, four 16-byte loads), thread 340 + u (u < 170) group 2 of
@@ -524,14 +457,9 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
         // lmaxp[0] = the maximum the scale is chosen from: running maximum of the segment so far (a restart folds the overflow
         // note in) joined by plane zfirst.  Written only here, between this pass's two barriers; lmaxp[1] = overflow notes, written
         // only AFTER the second barrier and read behind the z loop's barriers.
-        if (tid == 0) { const unsigned note = lmaxp[1]; lmaxp[1] = 0u; if (note) atomicMax(lmaxp, note); }
+        x3_ring_fold_notes<1>(lmaxp, tid);
         prefetch(xb, zfirst); mat(zfirst);
-        const float wm = x3_wave_max(local_max());
-        if (lane == 0) atomicMax(lmaxp, __float_as_uint(wm));
-        __syncthreads();
-        mul = x3_pow2_scale(__uint_as_float(lmaxp[0]), X3_ACT_TARGET);
-        cap_bits = __float_as_uint(X3_F16_CAP / mul);      // (mul in [2^-101, 2^99]: finite)
-        if (tid < 32) par[tid] = par[96 + tid] * (1.f / mul);       // the epilogue's scale undoes the column's 2^-e
+        x3_ring_scale(lmaxp, par, local_max(), tid, mul, cap_bits);      // (a barrier inside)
         commit(zfirst % 3);
         prefetch(xb, zfirst - 1); mat(zfirst - 1); note_overflow(); commit((zfirst - 1 + 3) % 3);
         prefetch(xb, zfirst + 1);
@@ -648,8 +576,7 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
             const float sc4[4] = {tsc.x, tsc.y, tsc.z, tsc.w}, sh4[4] = {tsh.x, tsh.y, tsh.z, tsh.w};
             if (a.tail_g4) {      // G4 destination (four output channels: fill_tails): one 16-byte (bf16: 8-byte) store per voxel
               float u4[4];
-#pragma unroll
-              for (int r = 0; r < 4; ++r) { const float u = fmaf(tacc[r], sc4[r], sh4[r]); u4[r] = trelu ? fmaxf(u, 0.f) : u; }
+              x3_tail_bn(tacc, par, kb, trelu, u4);
               st4(tbase + ((int64_t)z * HW + (nt & 1) * 16) * 4, u4);
             } else {
               T* pt = tbase + (int64_t)z * HW + (nt & 1) * 16;
@@ -691,9 +618,6 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
         prefetch(xb, z + 2);
       }
       X3_STAMP(5);
-#ifdef RAGMI_DIAG
-      ++dg_steps;
-#endif
     }
       if (!again) break;
     }
@@ -705,13 +629,8 @@ __global__ __launch_bounds__(X3_THREADS, (NCG <= 3 ? 4 : 2)) void conv3d_x3_kern
 #ifdef RAGMI_DIAG
   if (dg_stamp) {
     X3_STAMP(6);
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0) {
-      unsigned long long* const o = x3_stamp_buf + ((int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * X3_WAVES + wave) * X3_STAMP_WORDS;
-      for (int k = 0; k < 7; ++k) o[k] = dg_sum[k];
-      o[7] = dg_steps; o[8] = dg_t0; o[9] = t1; o[10] = dg_r0; o[11] = r1;
-      o[12] = __builtin_amdgcn_s_getreg((4 << 11) | 20);      // HW_REG_XCC_ID (speed diagnostics only)
-    }
+    unsigned long long* const o = x3_stamp_flush(x3_stamp_buf, dg_sum, dg_steps, dg_t0, dg_r0, wave, lane);
+    if (o) o[12] = __builtin_amdgcn_s_getreg((4 << 11) | 20);      // HW_REG_XCC_ID (speed diagnostics only)
   }
 #endif
 }

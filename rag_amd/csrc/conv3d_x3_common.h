@@ -1,4 +1,4 @@
-// Shared pieces of the split-operand 3x3x3 convolution kernels (conv3d_x3.hip: z-marching and deep forms): operand splits, the MFMA wrapper, operand-scale helpers, packed-fragment layout and launch extras.
+// Shared pieces of the split-operand 3x3x3 convolution kernels (conv3d_x3.hip: z-marching and deep forms): operand splits, the MFMA wrapper, operand-scale helpers, packed-fragment layout, launch extras, and what conv3d_x3_kernel and conv3d_x3q_kernel (conv3d_x3q.hip) share besides the ring.
 #pragma once
 #include <cstdlib>
 
@@ -113,6 +113,43 @@ __device__ __forceinline__ float x3_wave_max(float m) {
   return __int_as_float(r);
 }
 
+// Profiling builds only (make DIAG=1; the shipped library has none of it): the RAGMI_X3_DIAG switches of the z-marching kernels, which
+// travel in bits 8..15 of K3Args::relu — 1 no stores, 2 no MFMA block, 4 no commit, 8 no loads, 16 operand reads at one address,
+// 32 in-kernel stamps, 64 no finishing step of the down-sampling tails, 128 no x blend + LDS parking — and the in-kernel stamps:
+// per wave the shader cycles (s_memtime) spent in each phase of its plane steps, summed over the launch, plus the wave's first / last
+// s_memtime and s_memrealtime (100 MHz): the clock the chip actually held is d(memtime) / d(memrealtime) x 100 MHz
+// (MI355X_MICROARCH.md, DVFS item 6).  The values go to a buffer of the kernel's own (one per translation unit: no relocatable device
+// code) that no kernel reads; nothing is computed from them.
+// X3_DIAG_DECODE(a.relu, buffer) at the top of a kernel declares the dg_* switches (constants in the shipped build, which never sees
+// the buffer's name) and the stamp state; X3_STAMP(k) adds the time since the previous stamp to phase k (6: everything outside the plane steps — ring start, item
+// decode; 5 closes a plane step, which is counted); x3_stamp_flush writes the wave's row at the end of the launch.
+constexpr int X3_STAMP_WORDS = 16;
+#ifdef RAGMI_DIAG
+#define X3_DIAG_DECODE(relu, stamp_buf)                                                                                                       \
+  const bool dg_nostore = ((relu) & 0x100) != 0, dg_nomfma = ((relu) & 0x200) != 0, dg_nocommit = ((relu) & 0x400) != 0,                       \
+             dg_noload = ((relu) & 0x800) != 0, dg_noread = ((relu) & 0x1000) != 0, dg_stamp = ((relu) & 0x2000) != 0 && (stamp_buf) != nullptr; \
+  [[maybe_unused]] const bool dg_nofinish = ((relu) & 0x4000) != 0, dg_nopark = ((relu) & 0x8000) != 0;                                        \
+  unsigned long long dg_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dg_last = 0, dg_t0 = 0, dg_r0 = 0;                                                  \
+  unsigned dg_steps = 0;                                                                                                                       \
+  if (dg_stamp) { dg_t0 = dg_last = __builtin_amdgcn_s_memtime(); dg_r0 = __builtin_amdgcn_s_memrealtime(); }
+#define X3_STAMP(k) do { if (dg_stamp) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+                                         dg_sum[k] += t_ - dg_last; dg_last = t_; if ((k) == 5) ++dg_steps; __builtin_amdgcn_sched_barrier(0); } } while (0)
+// the wave's row of the stamp buffer, written by lane 0 and returned to it (words from 12 on are the kernel's own); null elsewhere
+__device__ __forceinline__ unsigned long long* x3_stamp_flush(unsigned long long* stamp_buf, const unsigned long long (&sum)[8], unsigned steps,
+                                                              unsigned long long t0, unsigned long long r0, int wave, int lane) {
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+  if (lane != 0) return nullptr;
+  unsigned long long* const o = stamp_buf + ((int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * X3_WAVES + wave) * X3_STAMP_WORDS;
+  for (int k = 0; k < 7; ++k) o[k] = sum[k];
+  o[7] = steps; o[8] = t0; o[9] = t1; o[10] = r0; o[11] = r1;
+  return o;
+}
+#else
+#define X3_DIAG_DECODE(relu, stamp_buf) \
+  [[maybe_unused]] constexpr bool dg_nostore = false, dg_nomfma = false, dg_nocommit = false, dg_noload = false, dg_noread = false, dg_nofinish = false, dg_nopark = false
+#define X3_STAMP(k) do { } while (0)
+#endif
+
 // packed weight fragments of ONE accumulator set (a conv with Cout outputs and Cin = 4 * ncgs inputs):
 // wf[((cog * nsls + s) * 2 + hl) * 64 + lane] (uint4 = 8 halves): A[row = lane & 15][k = 8 (lane>>4) + j],
 // k -> pair P = 8 s + 2 (lane>>4) + (j>>2) = tap * ncgs + cg (TAP-MAJOR since round 4), channel 4 cg + (j&3); pairs past 27 * ncgs
@@ -184,15 +221,15 @@ struct X3StemSrc {
   const float* scale;        // stem3d0's folded BatchNorm (may be null: identity)
   const float* shift;
   int relu;
-  // one consumer 1x1x1 conv of stem3d0's output (4 output channels: cell 0's pre_preprocess), computed by the staging thread that
-  // owns the voxel (ntail == 0: none)
+  // one consumer 1x1x1 conv of stem3d0's output (4 output channels: cell 0's pre_preprocess; ntail == 0: none): rows 12..15 of the
+  // consumer's matrix product (tail_rows), or left to the combine kernel
   int ntail, tail_relu, tail_ch0, tail_g4;
   const float* tail_w;       // [4][Cm]
   const float* tail_scale;   // [4] (may be null)
   const float* tail_shift;
   float* tail_y;
   int64_t tail_bstride;
-  int tail_rows;              // the fused tail of stem3d0 is computed by rows 12..15 of the matrix product (RAGMI_TAIL_ROWS), not by the staging thread
+  int tail_rows;              // the fused tail of stem3d0 is computed by rows 12..15 of the matrix product (RAGMI_TAIL_ROWS), not by the combine kernel
 };
 
 struct X3Extra {
@@ -220,6 +257,115 @@ inline void x3_weight_sections(X3Extra& e, const K3Args& a, int nset, int dtype)
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// What the two z-marching kernels share besides the ring: conv3d_x3_kernel (conv3d_x3.hip, ring of three planes) and conv3d_x3q_kernel
+// (conv3d_x3q.hip, ring of four).  The fused tails' parameter prologue, the ring-start scale choice and the tails' BatchNorm live here
+// ONCE; locate / prefetch / commit / the K loop / the LDS layouts stay with each kernel.  A helper differs between its callers only by
+// plain arguments (a pointer, an index, a count, TAILS) — never by "which kernel am I".  (What else the two have in common is still
+// written out in both, and why: DESIGN.md 4.2.)
+//
+// Every descriptor array of the kernel arguments (K3Args, X3Extra: passed by const&, never copied into a local that a lane value
+// indexes) is indexed by a COMPILE-TIME index inside an unrolled loop and the lanes pick by comparison: indexed by a lane-dependent
+// value (set = i >> 4, tail = row >> 2) the compiler fetches the pointer itself with a vector load from the argument segment and the
+// value with a second, dependent one — ~25 serial memory round trips in front of the first plane of every launch (round 5: found in
+// the listing of the down-sampling tails' finishing step).
+// LDS parameter block `par` of both kernels (floats): scale[2 sets][16] (fp32 storage: times the column's 2^e, rewritten per ring
+// pass) | shift[2][16] @32 | tail scale[4 kb][4] @64 | tail shift[4][4] @80 | static scale[2][16] @96 (BatchNorm scale x the weights'
+// 2^-k) | @128 lmaxp: the maximum the operand scale is chosen from, then the words of overflow notes.
+// Down-sampling tails (TAILS == 2): plane copies of the x-blended tail values U[down slot 2][8 rows][16][4 ch] (X3_DU_PLANE floats each:
+// two by plane parity in conv3d_x3_kernel, three in conv3d_x3q_kernel) | x table [16]{w0, w1: weights of the source pair (2X, 2X+1)} |
+// y table [4]{...}
+constexpr int X3_DU_PLANE = 2 * 4 * X3_TY * (X3_TX / 2);
+
+// Fused consumer 1x1x1 convs ("tails") on the matrix cores: out_t[k][voxel] = sum_c W_t[k][c] * v[c][voxel] as four 16x16x4 fp32
+// products laid out so that every lane quarter feeds ITS OWN four channels (product r: channel 4 kb + r of each quarter), so no
+// value crosses lanes.  Rows: tail 0 -> 0..3, tail 1 -> 4..7, down-sampling tails after them.
+// (TAILS is compile time; the tail fragments and parameters live in LDS and are fetched in the epilogue — in registers they cost
+// ~20 VGPRs of a 128-VGPR budget and the main loop spilled)
+// (round 4: the tail products run on v_mfma_f32_16x16x4_f32 — four EXACT fp32 products — instead of three bf16 products of three-way
+// split operands: the splits were ~28 vector instructions per tile in a kernel bound by vector issue; the fp32 MFMA holds the issue
+// port for 8 of its 32 cycles)
+// Writes the A fragments ltail[4 products][64 lanes] and the tails' BatchNorm par[64..95].
+template <int TAILS>
+__device__ __forceinline__ void x3_tail_params(const K3Args& a, float* ltail, float* par, int cog, int tid) {
+  if (tid < 64) {
+    const int lane = tid, kb = lane >> 4;
+    const int row = lane & 15, tl = row >> 2, k = row & 3;     // lane & 15 is the A row: tail slot tl, its output channel k
+    float wv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const float* const pw = a.tail_w[t];
+      if (t < a.ntail && tl == t && k < a.tail_cout[t]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int c = cog * 16 + 4 * kb + j; if (c < a.Cout) wv[j] = pw[k * a.Cout + c]; }
+      }
+      if constexpr (TAILS == 2) {
+        const float* const pd = a.down_w[t];
+        if (t < a.ndown && tl == a.ntail + t && k < a.down_cout[t]) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { const int c = cog * 16 + 4 * kb + j; if (c < a.Cout) wv[j] = pd[k * a.Cout + c]; }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ltail[j * 64 + lane] = wv[j];
+  }
+  // this lane's tail outputs after that product: rows 4 kb + r -> tail slot kb (full-resolution tails first, then the down-sampling
+  // ones), output r
+  if (tid < 16) {
+    const int tk = tid >> 2, r = tid & 3;
+    float sc = 1.f, sh = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const float* const psc = a.tail_scale[t];
+      const float* const psh = a.tail_shift[t];
+      if (t < a.ntail && tk == t && r < a.tail_cout[t] && psc) { sc = psc[r]; sh = psh[r]; }
+      if constexpr (TAILS == 2) {
+        const float* const dsc = a.down_scale[t];
+        const float* const dsh = a.down_shift[t];
+        if (t < a.ndown && tk == a.ntail + t && r < a.down_cout[t] && dsc) { sc = dsc[r]; sh = dsh[r]; }
+      }
+    }
+    par[64 + tid] = sc;
+    par[80 + tid] = sh;
+  }
+}
+
+// Ring start (fp32 storage), first half, behind the pass's first barrier: lmaxp[0] = the maximum the scale is chosen from — the
+// running maximum of the segment so far; a restart folds the NOTES words of overflow notes in and clears them.  lmaxp[0] is written
+// only between a pass's two barriers; the note words only AFTER the second one, and they are read behind the z loop's barriers.
+template <int NOTES>
+__device__ __forceinline__ void x3_ring_fold_notes(unsigned* lmaxp, int tid) {
+  if (tid == 0) {
+    unsigned note = lmaxp[1];
+#pragma unroll
+    for (int w = 2; w <= NOTES; ++w) note = max(note, lmaxp[w]);
+#pragma unroll
+    for (int w = 1; w <= NOTES; ++w) lmaxp[w] = 0u;
+    if (note) atomicMax(lmaxp, note);
+  }
+}
+// ... second half: plane zfirst (this thread's largest scalable |x| of it: m) joins the maximum; behind the pass's second barrier every
+// thread derives the column's operand scale 2^-e — the largest |x| lands at 2^10..2^11, a factor >= 16 below fp16's range for the
+// planes that follow — and the bit pattern of X3_F16_CAP / mul, above which an element does not fit (mul in [2^-101, 2^99]: finite);
+// the epilogue's scale undoes the column's 2^-e.  lmaxp[0] only changes between the two barriers, so `mul` is workgroup-uniform.
+__device__ __forceinline__ void x3_ring_scale(unsigned* lmaxp, float* par, float m, int tid, float& mul, unsigned& cap_bits) {
+  const float wm = x3_wave_max(m);
+  if ((tid & 63) == 0) atomicMax(lmaxp, __float_as_uint(wm));
+  __syncthreads();
+  mul = x3_pow2_scale(__uint_as_float(lmaxp[0]), X3_ACT_TARGET);
+  cap_bits = __float_as_uint(X3_F16_CAP / mul);
+  if (tid < 32) par[tid] = par[96 + tid] * (1.f / mul);
+}
+
+// this lane quarter's four tail outputs: BatchNorm + ReLU of the tail product
+__device__ __forceinline__ void x3_tail_bn(const f32x4& tacc, const float* par, int kb, int trelu, float (&u4)[4]) {
+  const float4 tsc = *reinterpret_cast<const float4*>(par + 64 + 4 * kb), tsh = *reinterpret_cast<const float4*>(par + 80 + 4 * kb);
+  const float sc4[4] = {tsc.x, tsc.y, tsc.z, tsc.w}, sh4[4] = {tsh.x, tsh.y, tsh.z, tsh.w};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { const float u = fmaf(tacc[r], sc4[r], sh4[r]); u4[r] = trelu ? fmaxf(u, 0.f) : u; }
+}
 
 // conv3d_x3q.hip: the level-3 dual-cell form (four-slot ring, one barrier per plane step, immediate operand addresses)
 int xq_launch(const K3Args& a, const X3Extra& e, int nset, dim3 grid, hipStream_t st);

@@ -24,10 +24,10 @@ namespace ragmi {
 // (2 records behind every channel group and behind the hi copy: with strides that are multiples of 512 bytes hipcc fuses the reads of
 // the two sets / of a hi and its lo operand into ds_read2st64_b64 — half rate, and its result registers are not an MFMA operand)
 constexpr int XQ_RS = 40, XQ_PLS = X3_HY * XQ_RS, XQ_SLOTS = 4, XQ_CGS = XQ_SLOTS * XQ_PLS + 2, XQ_LOPAD = 2;      // records of 8 bytes
-constexpr int XQ_DU_SLOTS = 3, XQ_DU_PLANE = 2 * 4 * X3_TY * (X3_TX / 2);      // down-sampling tails: x-blended tail values, floats per plane copy
+constexpr int XQ_DU_SLOTS = 3;      // down-sampling tails: plane copies of the x-blended tail values (X3_DU_PLANE floats each)
 static_assert(XQ_RS >= X3_HX && (2 * XQ_RS) % 32 == 16 && XQ_PLS % 32 == 16, "bank layout: partners of an LDS pass 128 bytes mod 256 apart");
 static_assert((XQ_CGS * 8) % 512 != 0 && (XQ_PLS * 8) % 512 != 0 && XQ_PLS > 255, "strides that ds_read2(st64)_b64 cannot span");
-static_assert(2 * (2 * XQ_CGS + XQ_LOPAD) * 8 + 8 * 2 * 64 * 16 + 4 * 64 * 4 + 132 * 4 + XQ_DU_SLOTS * XQ_DU_PLANE * 4 + 20 * 16 <= 80 * 1024,
+static_assert(2 * (2 * XQ_CGS + XQ_LOPAD) * 8 + 8 * 2 * 64 * 16 + 4 * 64 * 4 + 132 * 4 + XQ_DU_SLOTS * X3_DU_PLANE * 4 + 20 * 16 <= 80 * 1024,
               "the dual launch with down-sampling tails must leave room for two workgroups per CU");
 // tap (dy * 3 + dx) that lane quarter q holds as operand j of a plane slice; the padding slot (q = 3, j = 1) re-reads its pass
 // partner's voxel.  Left over per plane: taps 4 = (1,1) and 5 = (1,2).
@@ -38,7 +38,7 @@ __host__ __device__ constexpr int xq_tap7(int q, int j) {
 __host__ __device__ constexpr bool xq_pad7(int q, int j) { return q == 3 && j == 1; }
 
 #ifdef RAGMI_DIAG
-// profiling builds: in-kernel stamps, as conv3d_x3.hip's (a buffer of its own per translation unit: no relocatable device code)
+// profiling builds: where the in-kernel stamps go (X3_DIAG_DECODE, conv3d_x3_common.h)
 __device__ unsigned long long* xq_stamp_buf = nullptr;
 extern "C" __attribute__((visibility("default"))) int ragmi_diag_x3q_stamp_buffer(void* buf) {
   unsigned long long* p = static_cast<unsigned long long*>(buf);
@@ -67,12 +67,10 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
   uint2* const llo = xq_lds + NCG * XQ_CGS + XQ_LOPAD;
   uint4* const lw = reinterpret_cast<uint4*>(xq_lds + 2 * (NCG * XQ_CGS + XQ_LOPAD));           // [slice][hi/lo][64 lanes]
   float* const ltail = reinterpret_cast<float*>(lw + NSL * 2 * 64);               // fused-tail A fragments [4 products][64 lanes] (fp32)
-  // scale[2][16] (times the column's 2^e, rewritten per ring pass) | shift[2][16] | tail scale[4 kb][4] | tail shift[4][4] |
-  // static scale[2][16] (BatchNorm scale x the weights' 2^-k) | lmaxp[3]: the maximum the scale is chosen from, two words of overflow notes
-  float* const par = ltail + 4 * 64;
+  float* const par = ltail + 4 * 64;               // parameter block, lmaxp[3] (two words of overflow notes), down staging: conv3d_x3_common.h
   unsigned* const lmaxp = reinterpret_cast<unsigned*>(par + 128);
   float* const ldu = par + 132;
-  float4* const ldxt = reinterpret_cast<float4*>(ldu + XQ_DU_SLOTS * XQ_DU_PLANE);
+  float4* const ldxt = reinterpret_cast<float4*>(ldu + XQ_DU_SLOTS * X3_DU_PLANE);
   float4* const ldyt = ldxt + X3_TX / 2;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, kb = lane >> 4;
   const int cog = blockIdx.y;
@@ -80,20 +78,7 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
   float act_floor = (a.relu & 1) ? 0.f : __builtin_nanf("");   // max(u, NaN) = u: the identity, NaN inputs included
   asm volatile("" : "+v"(act_floor));
   const int64_t DHW = (int64_t)HW * a.D;
-#ifdef RAGMI_DIAG
-  // profiling builds (RAGMI_X3_DIAG bits, as conv3d_x3_kernel): 1 no stores, 2 no MFMA block, 4 no commit, 8 no loads, 16 operand reads at one address
-  const bool dg_nostore = (a.relu & 0x100) != 0, dg_nomfma = (a.relu & 0x200) != 0, dg_nocommit = (a.relu & 0x400) != 0, dg_noload = (a.relu & 0x800) != 0, dg_noread = (a.relu & 0x1000) != 0;
-  const bool dg_nofinish = (a.relu & 0x4000) != 0, dg_nopark = (a.relu & 0x8000) != 0;      // 64: no finishing step of the down-sampling tails, 128: no x blend + LDS parking
-  const bool dg_stamp = (a.relu & 0x2000) != 0 && xq_stamp_buf != nullptr;
-  unsigned long long dg_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dg_last = 0, dg_t0 = 0, dg_r0 = 0;
-  unsigned dg_steps = 0;
-  if (dg_stamp) { dg_t0 = dg_last = __builtin_amdgcn_s_memtime(); dg_r0 = __builtin_amdgcn_s_memrealtime(); }
-#define XQ_STAMP(k) do { if (dg_stamp) { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-                                         dg_sum[k] += t_ - dg_last; dg_last = t_; __builtin_amdgcn_sched_barrier(0); } } while (0)
-#else
-  constexpr bool dg_nostore = false, dg_nomfma = false, dg_nocommit = false, dg_noload = false, dg_noread = false, dg_nofinish = false, dg_nopark = false;
-#define XQ_STAMP(k) do { } while (0)
-#endif
+  X3_DIAG_DECODE(a.relu, xq_stamp_buf);
   // weight fragments, 8 bytes (one pair's four channels) at a time, from the packed tap-major slices (x3_pack_one: pair P = tap, one
   // channel group per set) into this kernel's slices: [set][plane 0..2 | leftover]
   {
@@ -144,46 +129,7 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
     par[32 + tid] = sh;
   }
   if (tid < 3) lmaxp[tid] = 0u;
-  if constexpr (TAILS) {
-    if (tid < 64) {
-      const int row = n, tl = row >> 2, k = row & 3;     // n = lane & 15 is the A row: tail slot tl, its output channel k
-      float wv[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float* const pw = a.tail_w[t];
-        if (t < a.ntail && tl == t && k < a.tail_cout[t]) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { const int c = cog * 16 + 4 * kb + j; if (c < a.Cout) wv[j] = pw[k * a.Cout + c]; }
-        }
-        if constexpr (TAILS == 2) {
-          const float* const pd = a.down_w[t];
-          if (t < a.ndown && tl == a.ntail + t && k < a.down_cout[t]) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const int c = cog * 16 + 4 * kb + j; if (c < a.Cout) wv[j] = pd[k * a.Cout + c]; }
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ltail[j * 64 + lane] = wv[j];
-    }
-    if (tid < 16) {
-      const int tk = tid >> 2, r = tid & 3;      // tail slot tk (full-resolution tails first, then the down-sampling ones), output r
-      float sc = 1.f, sh = 0.f;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float* const psc = a.tail_scale[t];
-        const float* const psh = a.tail_shift[t];
-        if (t < a.ntail && tk == t && r < a.tail_cout[t] && psc) { sc = psc[r]; sh = psh[r]; }
-        if constexpr (TAILS == 2) {
-          const float* const dsc = a.down_scale[t];
-          const float* const dsh = a.down_shift[t];
-          if (t < a.ndown && tk == a.ntail + t && r < a.down_cout[t] && dsc) { sc = dsc[r]; sh = dsh[r]; }
-        }
-      }
-      par[64 + tid] = sc;
-      par[80 + tid] = sh;
-    }
-  }
+  if constexpr (TAILS) x3_tail_params<TAILS>(a, ltail, par, cog, tid);
   // Halo staging: thread t < 340 owns voxel t of the 10 x 34 halo plane for EVERY channel group (the groups are a wave-uniform
   // distance apart: one lane offset, one validity bit, one LDS record address); the threads past 340 stage nothing.
   const T* const x = static_cast<const T*>(a.x);
@@ -302,8 +248,8 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
         const float4 yt = ldyt[yp];
         // (THREE plane copies, plane z in copy z % 3: this step — after ONE barrier — reads the copies of planes zodd-1 and zodd while
         // the epilogues of this step already write plane zodd+1 into the third; with two copies a second barrier stood here)
-        const float* const u0 = ldu + ((zodd - 1) % 3) * XQ_DU_PLANE + ((dl * X3_TY + 2 * yp) * (X3_TX / 2) + xp) * 4 + r;
-        const float* const u1 = ldu + (zodd % 3) * XQ_DU_PLANE + ((dl * X3_TY + 2 * yp) * (X3_TX / 2) + xp) * 4 + r;
+        const float* const u0 = ldu + ((zodd - 1) % 3) * X3_DU_PLANE + ((dl * X3_TY + 2 * yp) * (X3_TX / 2) + xp) * 4 + r;
+        const float* const u1 = ldu + (zodd % 3) * X3_DU_PLANE + ((dl * X3_TY + 2 * yp) * (X3_TX / 2) + xp) * 4 + r;
         const float e0 = u0[0], e1 = u0[(X3_TX / 2) * 4], o0 = u1[0], o1 = u1[(X3_TX / 2) * 4];
         const int slot = a.ntail + dl;
         const float sc = par[64 + 4 * slot + r], sh = par[80 + 4 * slot + r];
@@ -376,14 +322,8 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
       for (int i = 0; i < X3_NT; ++i) {
         const int nt = wave * X3_NT + i;
         if (my_tail_cout > 0 && inside[i] && !(dg_nostore && tacc[i][0] != 12345.f)) {
-          const float4 tsc = *reinterpret_cast<const float4*>(par + 64 + 4 * kb), tsh = *reinterpret_cast<const float4*>(par + 80 + 4 * kb);
-          const float sc4[4] = {tsc.x, tsc.y, tsc.z, tsc.w}, sh4[4] = {tsh.x, tsh.y, tsh.z, tsh.w};
-          float u4[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {      // (xq_takes: every fused tail has exactly four output channels)
-            const float u = fmaf(tacc[i][r], sc4[r], sh4[r]);
-            u4[r] = my_trelu ? fmaxf(u, 0.f) : u;
-          }
+          float u4[4];      // (xq_takes: every fused tail has exactly four output channels)
+          x3_tail_bn(tacc[i], par, kb, my_trelu, u4);
           if constexpr (G4T) {
             *reinterpret_cast<float4*>(tptr + 64 * i) = make_float4(u4[0], u4[1], u4[2], u4[3]);
           } else {
@@ -403,7 +343,7 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
               ux[r] = lerp2(xt.x, xt.z != 0.f ? p1 : tacc[i][r], xt.y, p1);
             }
             if (!(n & 1))
-              reinterpret_cast<float4*>(ldu + (z % 3) * XQ_DU_PLANE)[(dl * X3_TY + (nt >> 1)) * (X3_TX / 2) + 8 * (nt & 1) + (n >> 1)] =
+              reinterpret_cast<float4*>(ldu + (z % 3) * X3_DU_PLANE)[(dl * X3_TY + (nt >> 1)) * (X3_TX / 2) + 8 * (nt & 1) + (n >> 1)] =
                   make_float4(ux[0], ux[1], ux[2], ux[3]);
           }
         }
@@ -415,9 +355,9 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
   // committed since the last check does not fit the column's operand scale): workgroup-uniform.
   auto step = [&](auto ph_, int z) -> bool {
     constexpr int PH = decltype(ph_)::value;
-    XQ_STAMP(6);
+    X3_STAMP(6);
     __syncthreads();                     // step z-1's operand reads are done (slot of plane z-2 is free); plane z+1 is in the LDS
-    XQ_STAMP(0);
+    X3_STAMP(0);
     if constexpr (TAILS == 2) {
       if (z > zs && !(z & 1)) down_finish(z - 1);      // planes z-2, z-1 of the x-blended tail values are complete (segments start even)
     }
@@ -428,11 +368,11 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
 #ifdef XQ_COMMIT_FIRST
     note_overflow(PH & 1);
     commit((PH + 2) & 3);                // plane z+2, first read at step z+1
-    XQ_STAMP(1);
+    X3_STAMP(1);
     prefetch(z + 3);                 // unconditional (addresses clamped): straight-line code ahead of the MFMA block
     __builtin_amdgcn_sched_barrier(0);
 #endif
-    XQ_STAMP(3);
+    X3_STAMP(3);
 #pragma unroll
     for (int st = 0; st < NSET; ++st)
 #pragma unroll
@@ -463,7 +403,7 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
 #pragma unroll
       for (int i = 0; i < X3_NT; ++i) acc[st][i] = x3_mma<false>(al, bh[i], acc[st][i]);
     }
-    XQ_STAMP(4);
+    X3_STAMP(4);
 #ifndef XQ_COMMIT_FIRST
     // Plane z+2 (in the registers since step z-1) goes to the ring AFTER the matrix block, not in front of it: vmcnt counts loads and
     // stores together and in order, and across the loop's back edge the compiler can only wait for vmcnt(0) — in front of the matrix
@@ -472,15 +412,12 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
     __builtin_amdgcn_sched_barrier(0);
     note_overflow(PH & 1);
     commit((PH + 2) & 3);                // plane z+2, first read at step z+1 (its slot was plane z-2's: free since the barrier above)
-    XQ_STAMP(1);
+    X3_STAMP(1);
     prefetch(z + 3);                     // unconditional (addresses clamped); consumed a whole step later
     __builtin_amdgcn_sched_barrier(0);
 #endif
     epilogue(z);
-    XQ_STAMP(5);
-#ifdef RAGMI_DIAG
-    ++dg_steps;
-#endif
+    X3_STAMP(5);
     return false;
   };
 #ifdef XQ_PHASE_OFFSET
@@ -545,14 +482,9 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
     // the ring (re)starts at plane zfirst with the operand scale chosen from that plane (conv3d_x3_kernel: same rule, same helpers)
     for (;;) {
       __syncthreads();
-      if (tid == 0) { const unsigned note = max(lmaxp[1], lmaxp[2]); lmaxp[1] = 0u; lmaxp[2] = 0u; if (note) atomicMax(lmaxp, note); }
+      x3_ring_fold_notes<2>(lmaxp, tid);
       prefetch(zfirst);
-      const float wm = x3_wave_max(local_max_of(pf, valid));
-      if (lane == 0) atomicMax(lmaxp, __float_as_uint(wm));
-      __syncthreads();
-      mul = x3_pow2_scale(__uint_as_float(lmaxp[0]), X3_ACT_TARGET);
-      cap_bits = __float_as_uint(X3_F16_CAP / mul);
-      if (tid < 32) par[tid] = par[96 + tid] * (1.f / mul);       // the epilogue's scale undoes the column's 2^-e
+      x3_ring_scale(lmaxp, par, local_max_of(pf, valid), tid, mul, cap_bits);      // (a barrier inside)
       commit(zfirst & 3);
       // (the ring start's notes are read by step zfirst: the word of "step zfirst - 1")
       prefetch(zfirst - 1); note_overflow((zfirst + 1) & 1); commit((zfirst + 3) & 3);
@@ -582,20 +514,15 @@ __global__ __launch_bounds__(X3_THREADS, 4) void conv3d_x3q_kernel(K3Args a, X3E
   }
 #ifdef RAGMI_DIAG
   if (dg_stamp) {
-    XQ_STAMP(6);
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (lane == 0) {
-      unsigned long long* const o = xq_stamp_buf + ((int64_t)(blockIdx.y * gridDim.x + blockIdx.x) * X3_WAVES + wave) * 16;
-      for (int k = 0; k < 7; ++k) o[k] = dg_sum[k];
-      o[7] = dg_steps; o[8] = dg_t0; o[9] = t1; o[10] = dg_r0; o[11] = r1;
-    }
+    X3_STAMP(6);
+    x3_stamp_flush(xq_stamp_buf, dg_sum, dg_steps, dg_t0, dg_r0, wave, lane);
   }
 #endif
 }
 
 size_t xq_lds_bytes(int nset, bool down) {
   return (size_t)2 * (nset * XQ_CGS + XQ_LOPAD) * sizeof(uint2) + (size_t)4 * nset * 2 * 64 * sizeof(uint4) + 4 * 64 * sizeof(float) + 132 * sizeof(float) +
-         (down ? (size_t)(XQ_DU_SLOTS * XQ_DU_PLANE) * sizeof(float) + (size_t)(X3_TX / 2 + X3_TY / 2) * sizeof(float4) : 0);
+         (down ? (size_t)(XQ_DU_SLOTS * X3_DU_PLANE) * sizeof(float) + (size_t)(X3_TX / 2 + X3_TY / 2) * sizeof(float4) : 0);
 }
 
 // the shapes conv3d_x3q_kernel serves among those x3_eligible takes (k3_route asks; x3_launch makes the work list)

@@ -129,7 +129,7 @@ _STEM_TAIL_ROWS = [os.environ.get("RAGMI_STEM_TAIL_ROWS", "1") != "0"]      # th
 
 def set_stem_tail_rows(enabled: bool) -> None:
     """Whether the fused stems compute cell 0's pre_preprocess in the four idle rows of stem3d1's 12-channel matrix product (a
-    split-operand product, the RAGMI_F32X3 bound) instead of the exact fp32 chain in the staging thread."""
+    split-operand product, the RAGMI_F32X3 bound) instead of the exact fp32 chain of the combine kernel."""
     _STEM_TAIL_ROWS[0] = bool(enabled)
 
 
