@@ -642,6 +642,18 @@ int64_t ragmi_sgd_workspace_bytes(void);
 int ragmi_sgd_clip_step(void* param, void* grad, void* momentum_buf, int64_t n, float lr, float momentum, float weight_decay,
                         float max_norm, int first_step, void* workspace, void* norm_out, void* stream);
 
+/* The same step over the elements with active[i] != 0 only (active: n bytes on the device): the step of a supernet whose forward
+ * ran one sampled operation per edge (automl/mdenas_search.py:161-173).  torch.optim.SGD skips a parameter whose .grad is None -
+ * no weight decay, no momentum, momentum buffer created at that parameter's own first update - so p, g and buf of an inactive
+ * element are neither read nor written, and the norm and the clip coefficient are taken over the active elements only (all
+ * inactive: norm 0, nothing moves).  Active elements: g *= coef; d = g + weight_decay*p; buf = momentum*buf + d; p -= lr*buf.
+ * There is no first_step: momentum_buf must start at zero, and an element's first update then gives buf = d exactly.  With every
+ * byte non-zero the result equals ragmi_sgd_clip_step(first_step = 0) bit for bit.  Two launches, fp64 partial sums in a fixed
+ * order, no atomics, no memset.  RAGMI_EINVAL before any launch: a NULL param / grad / momentum_buf / active / workspace, n <= 0,
+ * a negative lr / momentum / weight_decay. */
+int ragmi_sgd_clip_step_masked(void* param, void* grad, void* momentum_buf, const void* active, int64_t n, float lr, float momentum,
+                               float weight_decay, float max_norm, void* workspace, void* norm_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------------
  * Batch preparation on the device (the reference's loaders: src/dataloaders/data_io.py:6-13, stereo_dataset.py:35-38, 57-121;
  * src_self/dataloaders/sceneflow_driving_dataset.py:53-70), ONE launch per batch:

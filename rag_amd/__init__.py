@@ -21,8 +21,9 @@ from .modules import Cell_2d, ConvBR_2d, OPS_2d, PRIMITIVES  # noqa: E402,F401
 from .network import Network  # noqa: E402,F401
 from . import checkpoint  # noqa: E402,F401
 from . import supernet  # noqa: E402,F401
-from .supernet import AutoFeature, AutoMatching, BasicNetwork  # noqa: E402,F401
+from .supernet import AutoFeature, AutoMatching, BasicNetwork, DepthAutoMatching, DepthBasicNetwork  # noqa: E402,F401
 from . import depth  # noqa: E402,F401
+depth.BasicNetwork = DepthBasicNetwork      # the depth tree's own name for its supernet (rag_depth/src/automl/mdenas_basicmodel.py)
 from .depth import DepthNetwork, load_depth_checkpoint  # noqa: E402,F401
 from . import data  # noqa: E402,F401
 from .data import color_stats, lanczos_taps, prepare_batch, random_crop_origin, resize_lanczos, resize_lanczos_torch, transfer_color  # noqa: E402,F401

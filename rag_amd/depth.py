@@ -34,6 +34,7 @@ from .modules import _CELL3D_ARCH, _ConvBR, ALL_CONV_ROWS, Cell_2d, ConvBR_2d, G
 from .network import Network as _StereoNetwork
 
 MAX_DEPTH = 80          # rag_model.py:298
+FP32_ONLY = "rag_amd.depth.Network: fp32 only (bf16 activation storage is not built for the depth network)"
 DEPTH_NAMES = ("silog_loss", "silog", "abs_rel", "log10", "rms", "sq_rel", "log_rms", "d1", "d2", "d3")
 
 
@@ -183,7 +184,7 @@ class Network(_StereoNetwork):
             raise RuntimeError("rag_amd.depth.Network: forward is inference only; call it under torch.no_grad() with the model in "
                                "eval(), or train through Network.forward_train (rag_amd.train.train_step drives it)")
         if self.act_dtype != torch.float32 or x.dtype != torch.float32:
-            raise RuntimeError("rag_amd.depth.Network: fp32 only (bf16 activation storage is not built for the depth network)")
+            raise RuntimeError(FP32_ONLY)
 
     def _trunk(self, x, stem0, stem1, cells, m6, m12, train: bool = False) -> torch.Tensor:
         """stem3d0 -> stem3d1 -> cells (rag_model.py:363-373), then the head's 1x1 part: the input of upsample_6, at (h/2, w/2) or

@@ -1053,6 +1053,29 @@ def sgd_clip_step(param: torch.Tensor, grad: torch.Tensor, buf: torch.Tensor, lr
     return norm_out
 
 
+def sgd_clip_step_masked(param: torch.Tensor, grad: torch.Tensor, buf: torch.Tensor, active: torch.Tensor, lr: float, momentum: float,
+                         weight_decay: float, max_norm: float, workspace: Optional[torch.Tensor] = None,
+                         norm_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sgd_clip_step over the elements with active[i] != 0 only (ragmi_sgd_clip_step_masked): `active` is a flat uint8 (or bool)
+    device tensor of the buffers' length; inactive elements of param / grad / buf are not touched, the norm is over the active ones.
+    `buf` must have started at zero (there is no first_step).  Returns the 1-element total-norm tensor."""
+    _need_gpu(param, grad, buf, workspace, norm_out)
+    for t in (param, grad, buf):
+        if t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != param.numel():
+            raise RuntimeError("sgd_clip_step_masked: param / grad / momentum buffers must be flat contiguous fp32 of equal length")
+    if not active.is_cuda or active.dim() != 1 or active.dtype not in (torch.uint8, torch.bool) or not active.is_contiguous() or active.numel() != param.numel():
+        raise RuntimeError("sgd_clip_step_masked: active must be a flat contiguous uint8 / bool device tensor of the buffers' length")
+    lib = load_library()
+    if workspace is None:
+        workspace = torch.empty((lib.ragmi_sgd_workspace_bytes() // 4,), device=param.device, dtype=torch.float32)
+    if norm_out is None:
+        norm_out = torch.empty((1,), device=param.device, dtype=torch.float32)
+    check(lib.ragmi_sgd_clip_step_masked(param.data_ptr(), grad.data_ptr(), buf.data_ptr(), active.data_ptr(), param.numel(), float(lr),
+                                         float(momentum), float(weight_decay), float(max_norm), workspace.data_ptr(),
+                                         norm_out.data_ptr(), _stream()), "sgd_clip_step_masked")
+    return norm_out
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # monocular-depth network (rag_depth): fused head and loss + metrics
 def depth_head_supported(cin: int, hi: int, wi: int, h: int, w: int, scale: int = 3, dtype=torch.float32) -> bool:

@@ -8,6 +8,11 @@ grown network — ConvBR (1x1, 3x3), identity, (bi/tri)linear resize, sum, conca
 `rag_amd.modules` / `rag_amd.autograd`: class names, constructor signatures, attribute names and therefore state_dict
 keys follow the reference (a reference supernet checkpoint loads strictly), and both inference and the search's
 training step (mdenas_search.py:164-173) run on the HIP kernels.  2-D cells run on depth-1 volumes like `Cell_2d`.
+
+The monocular-depth search (rag_depth/src/automl/mdenas_basicmodel.py) runs on `DepthBasicNetwork`: the same `AutoFeature`, a 2-D
+`DepthAutoMatching` (rag_depth/src/automl/build_model_3d.py:157-275; no cost volume, `right` is ignored) and the fused depth head of
+`rag_amd.depth`.  `active_parameters(fea_ops, mat_ops)` of either supernet names the parameters one sampled forward reaches: what
+`rag_amd.train`'s sampled-op step hands to the optimizer (torch.optim.SGD skips the others, whose .grad is None).
 """
 from __future__ import annotations
 
@@ -21,7 +26,8 @@ import torch.nn.functional as F
 
 from . import autograd as ag
 from . import ops
-from .modules import (OPS_2d, OPS_3d, PRIMITIVES, PRIMITIVES_3D, ConvBR_2d, ConvBR_3d, Disp, Genotype, MatchingNet)
+from .depth import FP32_ONLY, MAX_DEPTH, DepthHeadFn, DispHead
+from .modules import (OPS_2d, OPS_3d, PRIMITIVES, PRIMITIVES_3D, ConvBR_2d, ConvBR_3d, Disp, Genotype, MatchingNet, _ConvBR)
 
 
 def _resize(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
@@ -42,6 +48,14 @@ def _sum(parts):
             a, b = acc.contiguous(), h.contiguous()
             acc = ops.add(a, 0, b, 0, torch.empty_like(a), 0, a.shape[1])
     return acc
+
+
+def _unit_parameters(unit) -> list:
+    """The parameters a ConvBR's forward reads: the weight, and the BatchNorm affine unless bn=False (that unit constructs a
+    BatchNorm it never calls); an identity has none."""
+    if not isinstance(unit, _ConvBR):
+        return []
+    return [unit.conv.weight] + ([unit.bn.weight, unit.bn.bias] if unit.use_bn else [])
 
 
 class _MixedOp(nn.Module):
@@ -132,6 +146,18 @@ class _SuperCell(nn.Module):
             final_concates.append(torch.cat(states[-self.block_multiplier:], dim=1))
         return final_concates
 
+    def active_parameters(self, has_s0: bool, variant: str, n_alphas) -> list:
+        """Parameters that forward(s0 if has_s0 else None, <the s1 argument named by `variant`>, n_alphas) reads: that variant's
+        preprocessor, pre_preprocess when there is an s0 (its channel count never equals C_out), and the selected op of every
+        edge (every step's state is concatenated into the output, so every edge is on the path)."""
+        out = _unit_parameters(getattr(self, "preprocess_" + variant))
+        if has_s0 and self.C_prev_prev != self.C_out:
+            out += _unit_parameters(self.pre_preprocess)
+        for k, op in enumerate(self._ops):
+            if op is not None:
+                out += _unit_parameters(op._ops[int(n_alphas[k])])
+        return out
+
 
 class SuperCell_3d(_SuperCell):
     CONV, MIXED = ConvBR_3d, MixedOp_3d
@@ -158,8 +184,25 @@ def _head(mod, last, d, h, w):
     raise ValueError("supernet head: unsupported size (H and W must be multiples of 12)")   # the reference: unbound `mat`
 
 
+def _search_net_active(mod, n_alphas) -> list:
+    """active_parameters of AutoMatching / AutoFeature: stems, every cell as `mod.WIRING` calls it, the `last_*` of `mod.HEAD`."""
+    out = []
+    for name in mod.STEMS + mod.HEAD:
+        out += _unit_parameters(getattr(mod, name))
+    for cell, (has_s0, variant) in zip(mod.cells, mod.WIRING):
+        out += cell.active_parameters(has_s0, variant, n_alphas)
+    return out
+
+
 class AutoMatching(nn.Module):
     """automl/build_model_3d.py:155-275; network architecture levels [0,0,0,1,2,1,2,2]."""
+    STEMS = ("stem0",)
+    # per cell: (an s0 is passed, which s1 argument is passed) in forward below; the last cell is at level 2 (1/12 of the image),
+    # so _head takes the last_12 -> last_6 -> last_3 branch and last_24 is never called
+    WIRING = ((False, "same"), (True, "same"), (True, "same"), (True, "down"), (True, "down"), (True, "up"), (True, "down"),
+              (True, "same"))
+    HEAD = ("last_12", "last_6", "last_3")
+    CONV = ConvBR_3d
 
     def __init__(self, num_layers=8, filter_multiplier=4, block_multiplier=3, step=3, cell=SuperCell_3d):
         super().__init__()
@@ -168,19 +211,22 @@ class AutoMatching(nn.Module):
         self._block_multiplier, self._filter_multiplier = block_multiplier, filter_multiplier
         f = int(filter_multiplier)
         self._num_end = f * block_multiplier
-        self.stem0 = ConvBR_3d(self._num_end * 2, self._num_end, 3, stride=1, padding=1)
+        self.stem0 = self.CONV(self._stem_in(), self._num_end, 3, stride=1, padding=1)
         # (prev_prev, down, same, up, filter) per layer, build_model_3d.py:172-211
         spec = [(-1, None, f, None, f), (f, None, f, f * 2, f), (f, None, f, f * 2, f), (f, f, f * 2, f * 4, f * 2),
                 (f, f * 2, f * 4, f * 8, f * 4), (f * 2, f, f * 2, f * 4, f * 2), (f * 4, f * 2, f * 4, f * 8, f * 4),
                 (f * 2, f * 2, f * 4, f * 8, f * 4)]
         for i in range(num_layers):
             self.cells.append(cell(step, block_multiplier, *spec[min(i, 7)]))
-        self.last_3 = ConvBR_3d(self._num_end, 1, 3, 1, 1, bn=False, relu=False)
-        self.last_6 = ConvBR_3d(self._num_end * 2, self._num_end, 1, 1, 0)
-        self.last_12 = ConvBR_3d(self._num_end * 4, self._num_end * 2, 1, 1, 0)
-        self.last_24 = ConvBR_3d(self._num_end * 8, self._num_end * 4, 1, 1, 0)
+        self.last_3 = self.CONV(self._num_end, 1, 3, 1, 1, bn=False, relu=False)
+        self.last_6 = self.CONV(self._num_end * 2, self._num_end, 1, 1, 0)
+        self.last_12 = self.CONV(self._num_end * 4, self._num_end * 2, 1, 1, 0)
+        self.last_24 = self.CONV(self._num_end * 8, self._num_end * 4, 1, 1, 0)
 
-    def forward(self, x, n_alphas):
+    def _stem_in(self) -> int:
+        return self._num_end * 2                       # the cost volume: left and right features
+
+    def _cells(self, x, n_alphas):
         stem = self.stem0(x)
         c = self.cells
         l3, = c[0](None, None, stem, None, n_alphas)
@@ -191,12 +237,43 @@ class AutoMatching(nn.Module):
         l6, = c[5](l6, None, None, l12, n_alphas)
         l12_1, = c[6](l12, l6, None, None, n_alphas)
         l12_2, = c[7](l6, None, l12_1, None, n_alphas)
+        return l12_2
+
+    def forward(self, x, n_alphas):
         d, h, w = x.shape[2:]
-        return _head(self, l12_2, d, h, w)
+        return _head(self, self._cells(x, n_alphas), d, h, w)
+
+    def active_parameters(self, n_alphas) -> list:
+        return _search_net_active(self, n_alphas)
+
+
+class DepthAutoMatching(AutoMatching):
+    """rag_depth/src/automl/build_model_3d.py:157-275: AutoMatching over the left image's features instead of a cost volume - the
+    2-D `SuperCell_2d` (the depth tree's cell is line for line build_model_2d.py's) and `ConvBR_2d` under the same attribute names,
+    on depth-1 volumes.  `forward(x [B,12,h,w], n_alphas)` returns the input of upsample_6, last_6(upsample_12(last_12(.))) at
+    [B,12,h/2,w/2]: upsample_6 -> last_3 belong to the fused head launch of `DepthBasicNetwork` (ops.depth_head), so the
+    reference's `mat` is not materialised."""
+    CONV = ConvBR_2d
+
+    def __init__(self, num_layers=8, filter_multiplier=4, block_multiplier=3, step=3, cell=SuperCell_2d):
+        super().__init__(num_layers, filter_multiplier, block_multiplier, step, cell)
+
+    def _stem_in(self) -> int:
+        return self._num_end
+
+    def forward(self, x, n_alphas):
+        h, w = x.shape[2:]
+        last = self._cells(x.unsqueeze(2), n_alphas)
+        if tuple(last.shape[2:]) != (1, h // 4, w // 4):     # levels [0,0,0,1,2,1,2,2]: nothing else can come out for H, W % 12 == 0
+            raise ValueError("depth supernet head: unsupported size (H and W must be multiples of 12)")
+        return self.last_6(self.last_12(last), resample_to=(1, h // 2, w // 2)).squeeze(2)
 
 
 class AutoFeature(nn.Module):
     """automl/build_model_2d.py:155-240; levels [1,0,1,0]; input [B,3,H,W] -> features [B,12,H/3,W/3]."""
+    STEMS = ("stem0", "stem1", "stem2")
+    WIRING = ((False, "down"), (True, "up"), (True, "down"), (True, "up"))      # as forward below calls the cells
+    HEAD = ("last_3",)                                                          # the last cell is at level 0: _head's first branch
 
     def __init__(self, num_layers=4, filter_multiplier=4, block_multiplier=3, step=3, cell=SuperCell_2d):
         super().__init__()
@@ -225,36 +302,31 @@ class AutoFeature(nn.Module):
         l6_1, = c[2](l6, l3_1, None, None, n_alphas)
         l3_2, = c[3](l3_1, None, None, l6_1, n_alphas)
         _one, h, w = stem2.shape[2:]
-        return _head(self, l3_2, 1, h, w)[:, :, 0]
+        return _head(self, l3_2, 1, h, w).squeeze(2)       # (a select's backward is zeros + copy_: a memcpy node when captured)
+
+    def active_parameters(self, n_alphas) -> list:
+        return _search_net_active(self, n_alphas)
 
 
-class BasicNetwork(nn.Module):
-    """automl/mdenas_basicmodel.py:48-134: forward(left, right, fea_ops, mat_ops) -> disp; `p` holds the per-edge op
-    probabilities the MdeNAS search updates, `genotype()` reads the searched cell out of them."""
+class _SearchNetwork(nn.Module):
+    """What the stereo and the depth supernet share (mdenas_basicmodel.py of both trees): `feature`, `matching`, the per-edge op
+    probabilities `p` the MdeNAS search updates, `new()`, `genotype()`, and the parameter set of one sampled forward."""
 
-    def __init__(self, steps=3, multiplier=4, stem_multiplier=3, device="cuda:0", maxdisp: int = 192):
+    def __init__(self, steps=3, multiplier=4, stem_multiplier=3, device="cuda:0"):
         super().__init__()
         self._steps, self._multiplier, self.device = steps, multiplier, device
         self.num_ops = len(PRIMITIVES)
         self.num_edges = sum(1 for i in range(self._steps) for n in range(2 + i))
-        self.feature = AutoFeature()
-        self.matching = AutoMatching()
-        self.maxdisp = maxdisp                  # the reference hard-codes 192 (mdenas_basicmodel.py:63)
-        self.disp = Disp(self.maxdisp)
         self.p = None
         self._initialize_p()
 
+    def _clone_args(self) -> dict:
+        return {}
+
     def new(self):
-        model_new = BasicNetwork(device=self.device, maxdisp=self.maxdisp).to(self.device)
+        model_new = type(self)(device=self.device, **self._clone_args()).to(self.device)
         model_new.p = deepcopy(self.probability())
         return model_new
-
-    def forward(self, left, right, fea_ops, mat_ops):
-        x = self.feature(left, fea_ops)
-        y = self.feature(right, fea_ops)
-        cost = MatchingNet.cost_volume(self, x.contiguous(), y.contiguous())      # the loop of :83-91 as one kernel
-        cost = self.matching(cost, mat_ops)
-        return self.disp(cost)
 
     def _initialize_p(self):
         k, n = self.num_edges, self.num_ops
@@ -278,3 +350,71 @@ class BasicNetwork(nn.Module):
 
         return Genotype(normal=strongest_two(F.softmax(self.p["normal"], dim=-1).numpy()), normal_concat=None,
                         reduce=strongest_two(F.softmax(self.p["reduce"], dim=-1).numpy()), reduce_concat=None)
+
+    def _head_parameters(self) -> list:
+        return []
+
+    def active_parameters(self, fea_ops, mat_ops) -> list:
+        """The parameters that receive a gradient from a backward through forward(left, right, fea_ops, mat_ops): stems, the
+        preprocessors the cells use, the `last_*` on the head's path, the head, and the selected op of every edge - read off the
+        wiring (`WIRING` / `HEAD` of AutoFeature / AutoMatching), not off gradient values.  Not in the list: `matching.last_24`
+        and the Feature Net's `last_6/12/24` (never called), the BatchNorm affine of a bn=False unit, every op that was not
+        selected.  The reference leaves the .grad of exactly the others at None, and torch.optim.SGD then skips them
+        (mdenas_search.py:161-173)."""
+        return self.feature.active_parameters(fea_ops) + self.matching.active_parameters(mat_ops) + self._head_parameters()
+
+
+class BasicNetwork(_SearchNetwork):
+    """automl/mdenas_basicmodel.py:48-134: forward(left, right, fea_ops, mat_ops) -> disp; `p` holds the per-edge op
+    probabilities the MdeNAS search updates, `genotype()` reads the searched cell out of them."""
+
+    def __init__(self, steps=3, multiplier=4, stem_multiplier=3, device="cuda:0", maxdisp: int = 192):
+        super().__init__(steps, multiplier, stem_multiplier, device)
+        self.feature = AutoFeature()
+        self.matching = AutoMatching()
+        self.maxdisp = maxdisp                  # the reference hard-codes 192 (mdenas_basicmodel.py:63)
+        self.disp = Disp(self.maxdisp)
+
+    def _clone_args(self) -> dict:
+        return {"maxdisp": self.maxdisp}
+
+    def forward(self, left, right, fea_ops, mat_ops):
+        x = self.feature(left, fea_ops)
+        y = self.feature(right, fea_ops)
+        cost = MatchingNet.cost_volume(self, x.contiguous(), y.contiguous())      # the loop of :83-91 as one kernel
+        cost = self.matching(cost, mat_ops)
+        return self.disp(cost)
+
+
+class DepthBasicNetwork(_SearchNetwork):
+    """rag_depth/src/automl/mdenas_basicmodel.py:69-159: forward(left, right, fea_ops, mat_ops) -> depth [B, H, W] in metres =
+    DispHead(matching(feature(left)), 3) x max_depth.  `right` is ignored (the reference never reads it) and may be None.  The
+    head runs as in the grown depth network (rag_amd.depth.Network): upsample_6 -> last_3 -> DispHead -> x3 -> x max_depth is ONE
+    launch (ops.depth_head), `DepthHeadFn` under autograd.  fp32 only, no ATen fallback.  state_dict keys and shapes are the
+    reference's (`disp` has no parameters)."""
+
+    def __init__(self, steps=3, multiplier=4, stem_multiplier=3, device="cuda:0", max_depth: float = MAX_DEPTH):
+        super().__init__(steps, multiplier, stem_multiplier, device)
+        self.feature = AutoFeature()
+        self.matching = DepthAutoMatching()
+        self.maxdisp = 192                      # as the reference (mdenas_basicmodel.py:84-85): built, never used
+        self.disp = Disp(self.maxdisp)
+        self.depth_head = DispHead(input_dim=1)
+        self.max_depth = max_depth
+
+    def _clone_args(self) -> dict:
+        return {"max_depth": self.max_depth}
+
+    def _head_parameters(self) -> list:
+        return [self.depth_head.conv1.weight, self.depth_head.conv1.bias]
+
+    def forward(self, left, right, fea_ops, mat_ops):
+        if left.dtype != torch.float32:
+            raise RuntimeError(FP32_ONLY)
+        x = self.feature(left, fea_ops)
+        y6 = self.matching(x, mat_ops)
+        m3, dh = self.matching.last_3, self.depth_head.conv1
+        args = (x.shape[2:], 3, float(self.max_depth))
+        if ag.needs_grad(y6, m3.conv.weight, dh.weight, dh.bias):
+            return DepthHeadFn.apply(y6, m3.conv.weight, dh.weight, dh.bias, *args)
+        return ops.depth_head(y6, m3.conv.weight.detach(), dh.weight.detach(), dh.bias.detach(), *args)

@@ -6,10 +6,14 @@ bucket: the `.grad` of every trainable parameter is a view into `GradBucket.flat
 straight into the buffer RCCL reduces — no pack/unpack copies and a single collective per step (the message is
 < 1 MB, i.e. latency-bound on xGMI: one call is what matters).  Train-mode BatchNorm keeps
 per-replica statistics, like the single-GPU reference per replica.
+
+The cell search's step (automl/mdenas_search.py:161-173 of both trees) is the same sequence on a supernet with one sampled
+operation per edge: `sampled_ops=(fea_ops, mat_ops)`.  Only the sampled operations receive gradients and torch.optim.SGD skips a
+parameter whose .grad is None, so that step updates `net.active_parameters(fea_ops, mat_ops)` alone (FlatSGD.set_active).
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Optional
+from typing import Iterable, List, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -86,6 +90,30 @@ def _is_depth(net) -> bool:
     return isinstance(net, DepthNetwork)
 
 
+def _supernet_kind(net) -> Optional[str]:
+    from .supernet import BasicNetwork, DepthBasicNetwork
+    return "depth" if isinstance(net, DepthBasicNetwork) else "stereo" if isinstance(net, BasicNetwork) else None
+
+
+def _check_sampled(net, sampled_ops, gt, task_arch, features: bool, supervise: bool) -> Optional[str]:
+    """Argument checks of the sampled-op step, before any launch.  -> "stereo" / "depth" when `sampled_ops` is given, else None."""
+    kind = _supernet_kind(net)
+    if sampled_ops is None:
+        if kind is not None:
+            raise ValueError("a supernet runs one sampled operation per edge: pass sampled_ops=(fea_ops, mat_ops)")
+        return None
+    if kind is None:
+        raise ValueError("sampled_ops is the cell search's step: net must be rag_amd.BasicNetwork or rag_amd.DepthBasicNetwork")
+    if len(sampled_ops) != 2:
+        raise ValueError("sampled_ops must be the pair (fea_ops, mat_ops)")
+    if task_arch is not None or features or not supervise:
+        raise ValueError("sampled_ops: a supernet has no units to choose (task_arch), takes images (features=True is refused) and "
+                         "trains supervised (supervise=False is refused)")
+    if gt is None:
+        raise ValueError("sampled_ops: the search step needs the ground truth gt (disparity, or depth in metres with 0 = invalid)")
+    return kind
+
+
 def _check_supervision(gt, features: bool, supervise: bool, depth: bool = False) -> None:
     if depth:
         if not supervise or features:
@@ -104,7 +132,7 @@ TRAIN_PRECISION = "fp32"     # the reference's training step is fp32 (rag.py:204
 
 
 def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None, features: bool = False,
-                     precision: Optional[str] = None, supervise: bool = True):
+                     precision: Optional[str] = None, supervise: bool = True, sampled_ops: Optional[Sequence] = None):
     """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  A depth network (rag_amd.depth.Network):
     Network.forward_train(left) -> silog_loss(depth, gt) with gt the ground-truth depth in metres (0 = invalid) as in
     rag_depth/src/approaches/rag.py:232-242; `right` may be None.  `supervise=False`: the self-supervised loss
@@ -112,12 +140,25 @@ def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None
     the images (features=True raises ValueError).  `features=True`: `net` is a
     MatchingNet and left/right are Feature-Net outputs.  `precision`: arithmetic of the 3x3x3 convolutions of the step (forward and
     data gradient): "fp32" (default, TRAIN_PRECISION: every contraction on the fp32-input MFMA forms, the reference's arithmetic
-    class) or "f16x3" (opt-in; bound in include/rag_amd.h).  Returns the (detached) loss."""
+    class) or "f16x3" (opt-in; bound in include/rag_amd.h).  `sampled_ops=(fea_ops, mat_ops)`: `net` is a supernet
+    (rag_amd.BasicNetwork / DepthBasicNetwork) and the step is the cell search's (automl/mdenas_search.py:161-173): forward
+    net(left, right, fea_ops, mat_ops), masked smooth-L1 against net.maxdisp for the stereo supernet, silog_loss (gt > 0) for the
+    depth one; task_arch, features=True and supervise=False are refused, and so is a supernet without sampled_ops.  Returns the
+    (detached) loss."""
+    kind = _check_sampled(net, sampled_ops, gt, task_arch, features, supervise)
     depth = _is_depth(net)
-    _check_supervision(gt, features, supervise, depth)
+    if kind is None:
+        _check_supervision(gt, features, supervise, depth)
     from . import ops
     with ops.conv_precision(precision or TRAIN_PRECISION):
-        if depth:
+        if kind is not None:
+            out = net(left, right, sampled_ops[0], sampled_ops[1])
+            if kind == "depth":
+                from .depth import silog_loss
+                loss = silog_loss(out, gt)
+            else:
+                loss = masked_smooth_l1(out, gt, net.maxdisp)
+        elif depth:
             from .depth import silog_loss
             loss = silog_loss(net.forward_train(left, 0, task_arch if task_arch is not None else net.arch_init), gt)
         else:
@@ -132,7 +173,12 @@ class FlatSGD:
     """torch.optim.SGD(lr, momentum, weight_decay) of rag.py:64-70 over a GradBucket, with the parameters themselves moved
     into one flat buffer next to the flat gradient: clip_grad_norm_ + step is then ONE pair of HIP launches
     (ragmi_sgd_clip_step) instead of torch's multi-tensor launches over ~500 small tensors.  GPU only (no CPU fallback: on
-    the CPU use torch.optim.SGD via make_optimizer).  `param_groups[0]["lr"]` may be changed between steps like torch's."""
+    the CPU use torch.optim.SGD via make_optimizer).  `param_groups[0]["lr"]` may be changed between steps like torch's.
+
+    `set_active(params)`: the following steps update those parameters only (ragmi_sgd_clip_step_masked), as torch.optim.SGD does
+    when the .grad of every other parameter is None - no weight decay and no momentum on them, the norm over the active gradients,
+    and an unsampled parameter's momentum starts at its own first update (the momentum buffer starts at zero, which gives exactly
+    torch's lazily created buffer).  The choice holds until the next call; `set_active(None)` goes back to the whole buffer."""
 
     def __init__(self, bucket: GradBucket, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 3e-3):
         if not bucket.flat.is_cuda:
@@ -152,6 +198,30 @@ class FlatSGD:
         self._ops = ops
         self._ws = torch.empty((ops.load_library().ragmi_sgd_workspace_bytes() // 4,), device=self.flat.device, dtype=torch.float32)
         self.total_norm = torch.zeros((1,), device=self.flat.device, dtype=torch.float32)
+        self._offsets = {}
+        off = 0
+        for p in bucket.params:
+            self._offsets[id(p)] = (off, p.numel())
+            off += p.numel()
+        self._active_key, self._active_mask = None, None
+
+    def set_active(self, params: Optional[Iterable[torch.nn.Parameter]]) -> None:
+        """Restrict the following steps to `params` (each must be in the bucket); None: every parameter again.  The byte mask is
+        built on the host and copied to the device once per call (a repeated call with the same parameters keeps the mask)."""
+        if params is None:
+            self._active_key, self._active_mask = None, None
+            return
+        key = tuple(sorted(id(p) for p in params))
+        if key == self._active_key:
+            return
+        import numpy as np
+        mask = np.zeros((self.flat.numel(),), dtype=np.uint8)
+        for i in key:
+            if i not in self._offsets:
+                raise ValueError("FlatSGD.set_active: a parameter that is not in the optimizer's GradBucket")
+            off, n = self._offsets[i]
+            mask[off:off + n] = 1
+        self._active_key, self._active_mask = key, torch.from_numpy(mask).to(self.flat.device)
 
     def zero_grad(self, set_to_none: bool = False) -> None:
         self.bucket.zero()
@@ -159,8 +229,12 @@ class FlatSGD:
     def step(self, clip: float = 0.0) -> torch.Tensor:
         """clip_grad_norm_(clip) (clip <= 0: none) + SGD step; returns the pre-clip total gradient norm (device tensor)."""
         g = self.param_groups[0]
-        self._ops.sgd_clip_step(self.flat, self.bucket.flat, self.momentum_buffer, g["lr"], g["momentum"], g["weight_decay"], clip,
-                                self.steps == 0 or g["momentum"] == 0.0, self._ws, self.total_norm)
+        if self._active_mask is not None:
+            self._ops.sgd_clip_step_masked(self.flat, self.bucket.flat, self.momentum_buffer, self._active_mask, g["lr"], g["momentum"],
+                                           g["weight_decay"], clip, self._ws, self.total_norm)
+        else:
+            self._ops.sgd_clip_step(self.flat, self.bucket.flat, self.momentum_buffer, g["lr"], g["momentum"], g["weight_decay"], clip,
+                                    self.steps == 0 or g["momentum"] == 0.0, self._ws, self.total_norm)
         self.steps += 1
         torch.autograd.graph.increment_version(self.bucket.params)       # packed-weight caches key on ._version
         return self.total_norm
@@ -175,23 +249,41 @@ class FlatSGD:
         self.param_groups[0].update(sd["param_groups"][0])
 
 
-def exchange_and_update(optimizer, bucket: GradBucket, *, clip: float = 5.0, dist=None) -> None:
-    """gradient all-reduce (mean over replicas) -> clip_grad_norm_ -> optimizer step (rag.py:215-216)."""
+def exchange_and_update(optimizer, bucket: GradBucket, *, clip: float = 5.0, dist=None,
+                        active: Optional[Sequence[torch.nn.Parameter]] = None) -> None:
+    """gradient all-reduce (mean over replicas) -> clip_grad_norm_ -> optimizer step (rag.py:215-216).  `active` (the sampled-op
+    step): only these parameters are updated; the others and their momentum state stay bit for bit.  FlatSGD masks its fused
+    launch; for a torch optimizer the inactive parameters' .grad is None during optimizer.step() (their bucket slices are all
+    zero after the backward, so the clipping norm is already the active one) and the bucket's views are put back after it."""
     bucket.all_reduce_mean(dist)
     if isinstance(optimizer, FlatSGD):
+        if active is not None:
+            optimizer.set_active(active)
         optimizer.step(clip)
         return
     bucket.clip_(clip)
+    if active is None:
+        optimizer.step()
+        return
+    keep = {id(p) for p in active}
+    idle = [(p, p.grad) for p in bucket.params if id(p) not in keep]
+    for p, _g in idle:
+        p.grad = None
     optimizer.step()
+    for p, g in idle:
+        p.grad = g
 
 
 def train_step(net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
-               features: bool = False, precision: Optional[str] = None, supervise: bool = True):
-    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision` and `supervise` as in forward_backward
-    (defaults: fp32, supervised).  Returns the (detached) loss."""
+               features: bool = False, precision: Optional[str] = None, supervise: bool = True,
+               sampled_ops: Optional[Sequence] = None):
+    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision`, `supervise` and `sampled_ops` as in
+    forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops` the optimizer updates
+    net.active_parameters(*sampled_ops) only (exchange_and_update).  Returns the (detached) loss."""
     loss = forward_backward(net, bucket, left, right, gt, task_arch=task_arch, features=features, precision=precision,
-                            supervise=supervise)
-    exchange_and_update(optimizer, bucket, clip=clip, dist=dist)
+                            supervise=supervise, sampled_ops=sampled_ops)
+    active = net.active_parameters(*sampled_ops) if sampled_ops is not None else None
+    exchange_and_update(optimizer, bucket, clip=clip, dist=dist, active=active)
     return loss
 
 
@@ -221,23 +313,34 @@ class GraphedTrainStep:
     (ragmi_graph_node_census) and a capture holding any memcpy / memset node is refused — an ATen op that starts lowering to
     copy_ or memset after a torch upgrade fails loudly here instead of corrupting a replay.  The graph replays on the caller's
     current stream; no private stream is involved.  `supervise=False`: the self-supervised step of src_self (gt may be None).
-    A depth network: the silog step of forward_backward (right may be None)."""
+    A depth network: the silog step of forward_backward (right may be None).
+
+    `sampled_ops=(fea_ops, mat_ops)`: the cell search's step on a supernet (forward_backward).  The search keeps its ops for an
+    epoch, so it builds one object per epoch over the same bucket and optimizer (momentum carries over); the warm-up steps are real
+    steps on the given batch, so with warmup=1 the constructor IS the epoch's first step, `first_loss` is its loss, and later calls
+    replay.  Batch size 1 stays refused by the census as for the grown network (torch.cat of 5-D tensors is a copy there)."""
 
     def __init__(self, net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
-                 features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True):
-        _check_supervision(gt, features, supervise, _is_depth(net))
+                 features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True,
+                 sampled_ops: Optional[Sequence] = None):
+        if _check_sampled(net, sampled_ops, gt, task_arch, features, supervise) is None:
+            _check_supervision(gt, features, supervise, _is_depth(net))
+        self._active = net.active_parameters(*sampled_ops) if sampled_ops is not None else None
         self.net, self.opt, self.bucket, self.clip, self.dist = net, optimizer, bucket, clip, dist
         self.left = left.clone()
         self.right = right.clone() if right is not None else None
         self.gt = gt.clone() if gt is not None else None
         self.precision = precision or TRAIN_PRECISION
-        kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise)
+        kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise, sampled_ops=sampled_ops)
+        self.first_loss = None                         # loss of the first warm-up step (a real step on the given batch)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                  # warm-up on a side stream: lazy state (allocator pools, occupancy
             for _ in range(max(warmup, 1)):            # queries, momentum buffers) exists before capture
-                forward_backward(net, bucket, self.left, self.right, self.gt, **kw)
-                exchange_and_update(optimizer, bucket, clip=clip, dist=dist)
+                loss = forward_backward(net, bucket, self.left, self.right, self.gt, **kw)
+                exchange_and_update(optimizer, bucket, clip=clip, dist=dist, active=self._active)
+                if self.first_loss is None:
+                    self.first_loss = loss
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True)     # keep the hipGraph_t: its nodes are inspected below
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):   # RCCL's watchdog thread must not trip it
@@ -264,7 +367,7 @@ class GraphedTrainStep:
         self.graph.replay()
         if self._bn_buffers:
             torch.autograd.graph.increment_version(self._bn_buffers)
-        exchange_and_update(self.opt, self.bucket, clip=self.clip, dist=self.dist)
+        exchange_and_update(self.opt, self.bucket, clip=self.clip, dist=self.dist, active=self._active)
         return self.loss
 
 
