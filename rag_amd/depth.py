@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import ops
 from .checkpoint import _HEADS, _check_cell_pattern, _genotype, _unit_counts
-from .modules import _CELL3D_ARCH, _ConvBR, ALL_CONV_ROWS, Cell_2d, ConvBR_2d, Genotype, _volume
+from .modules import _CELL3D_ARCH, _ConvBR, ALL_CONV_ROWS, Cell_2d, ConvBR_2d, Genotype, _head_quarter, _plan_head
 from .network import Network as _StereoNetwork
 
 MAX_DEPTH = 80          # rag_model.py:298
@@ -203,20 +203,12 @@ class Network(_StereoNetwork):
         if last.shape[2] != h // 4:
             raise ValueError("rag_amd.depth.Network: feature height must be a multiple of 4 (input H a multiple of 12)")
         half = (1, h // 2, w // 2)
+        if train:
+            return m6(m12(last), resample_to=half)
+        # the stereo head's 1/4-level step on a depth-1 volume (one launch for last_12_3d and last_6_3d's channel mix where it is built)
         last5 = last.unsqueeze(2)
-        if (not train and m12._geometry() == 1 and m6._geometry() == 1 and ops.chain_k1_enabled() and _volume(half) > _volume(last5.shape[2:])
-                and m6.conv.out_channels <= m6.conv.in_channels
-                and ops.conv3d_k1_chain_supported(m12.conv.in_channels, m12.conv.out_channels, m6.conv.out_channels)):
-            # last_12_3d and last_6_3d's channel mix as ONE launch on the small volume, then the upsample_12 + ReLU (as the stereo head)
-            w1, s1, h1 = m12.prepared()
-            w2, s2, h2 = m6.prepared()
-            B = last.shape[0]
-            low = torch.empty((B, m6.conv.out_channels) + tuple(last5.shape[2:]), device=last.device, dtype=last.dtype)
-            ops.conv3d_k1_chain(last5, w1, s1, h1, m12.relu, w2, s2, h2, False, low)
-            y = torch.empty((B, m6.conv.out_channels) + half, device=last.device, dtype=last.dtype)
-            ops.trilinear3d_act(low, half, True, m6.relu, y, 0)
-            return y[:, :, 0]
-        return m6(m12(last), resample_to=half)
+        plan = _plan_head((1, h, w), last5.shape[2:], last.dtype, None, m6, m12, False)
+        return _head_quarter(last5, m12, m6, half, plan)[:, :, 0]
 
     def _head(self, y6, size, m3) -> torch.Tensor:
         if m3.use_bn or m3.relu or m3._geometry() != 3 or m3.conv.out_channels != 1:

@@ -321,6 +321,23 @@ class Disp(nn.Module):
         return ops.disp_softargmin(x, self.maxdisp)
 
 
+def _scale_dimension(dim, scale):
+    """rag_model.py:140-141 (and build_model_3d.py's cell): the size of one axis after a x0.5 / x2 resample."""
+    return int((float(dim) - 1.0) * scale + 1.0) if dim % 2 == 1 else int(float(dim) * scale)
+
+
+# What one cell launches behind its two 1x1x1 preprocess convs, as data (_Cell._schedule): a tuple of these steps, issued in order by
+# _Cell._run.  States are indices (0 = s0, 1 = s1, 2.. = the new states; _Cell._layout places each in a buffer), never tensors.
+#   Dual: ONE dual-input launch, state k = relu(bn(conv_a(s0))) + relu(bn(conv_b(s1))) for every k of dst_states (a_mods / b_mods stacked).
+#   Conv: one 3x3x3 launch on state `src` with the sibling convs `mods` stacked; unit i writes dst_states[i] (all in one buffer) and, where
+#         res_states is not None, adds res_states[i] (the running sum of its target, or an identity partner that is already complete).
+#   Add:  dst = a + b.      Copy: dst = src (a lone identity branch).
+Dual = namedtuple("Dual", "a_mods b_mods dst_states")
+Conv = namedtuple("Conv", "src mods dst_states res_states")
+Add = namedtuple("Add", "a b dst")
+Copy = namedtuple("Copy", "src dst")
+
+
 class _Cell(nn.Module):
     """Shared executor of Cell_3d (rag_model.py:114-177) and Cell_2d (:47-111) on HIP kernels; tensors are 5-D
     (the 2-D cell runs on depth-1 volumes: scale_dimension(1, s) == 1, and trilinear with one plane is bilinear).
@@ -359,23 +376,110 @@ class _Cell(nn.Module):
         raise NotImplementedError
 
     def scale_dimension(self, dim, scale):
-        return int((float(dim) - 1.0) * scale + 1.0) if dim % 2 == 1 else int(float(dim) * scale)
+        return _scale_dimension(dim, scale)
 
     def _contributions(self) -> Dict[int, List[Tuple[int, nn.Module]]]:
-        """new-state index -> [(source state j, op module)] in the reference's visit order."""
-        selected = set(int(v) for v in np.asarray(self._rows())[:, 0])
-        contribs: Dict[int, List[Tuple[int, nn.Module]]] = {}
-        offset, n_states, ops_index = 0, 2, 0
-        for _ in range(self._steps):
-            lst = []
-            for j in range(n_states):
-                if offset + j in selected:
-                    lst.append((j, self._ops[ops_index]))
-                    ops_index += 1
-            contribs[n_states] = lst
-            offset += n_states
-            n_states += 1
+        """new-state index -> [(source state j, op module)] in the reference's visit order (computed once: rows and _ops never
+        change after construction; kept in __dict__, out of the module tree)."""
+        contribs = self.__dict__.get("_contribs_cache")
+        if contribs is None:
+            selected = set(int(v) for v in np.asarray(self._rows())[:, 0])
+            contribs = {}
+            offset, n_states, ops_index = 0, 2, 0
+            for _ in range(self._steps):
+                lst = []
+                for j in range(n_states):
+                    if offset + j in selected:
+                        lst.append((j, self._ops[ops_index]))
+                        ops_index += 1
+                contribs[n_states] = lst
+                offset += n_states
+                n_states += 1
+            self.__dict__["_contribs_cache"] = contribs
         return contribs
+
+    def _layout(self, s0_in_pre: bool) -> Tuple[Tuple[str, int], ...]:
+        """(buffer, first channel) of every state: s0 in the cell's s0|s1 buffer "pre" (it went through pre_preprocess) or in its own
+        tensor "s0", s1 in "pre", the last block_multiplier new states in the concat "cat", earlier ones in "scratch"."""
+        C, first_cat = self.C_out, 2 + self._steps - self.block_multiplier
+        return ((("pre", 0) if s0_in_pre else ("s0", 0)), ("pre", C)) + tuple(
+            ("cat", (k - first_cat) * C) if k >= first_cat else ("scratch", (k - 2) * C) for k in range(2, 2 + self._steps))
+
+    def _schedule(self, s0_in_pre: bool) -> tuple:
+        """The cell's launches behind the preprocess stage as a tuple of Dual / Conv / Add / Copy steps: a property of the genotype
+        rows, steps, block_multiplier and of whether s0 sits in the s0|s1 buffer; touches no tensor.  Cached per s0_in_pre."""
+        cache = self.__dict__.setdefault("_schedule_cache", {})
+        key = bool(s0_in_pre)
+        if key not in cache:
+            cache[key] = self._build_schedule(key)
+        return cache[key]
+
+    def _build_schedule(self, s0_in_pre: bool) -> tuple:
+        contribs = self._contributions()
+        where = self._layout(s0_in_pre)
+        n_states = 2 + self._steps
+        first_cat = n_states - self.block_multiplier             # first state that lands in the concat buffer
+        steps: list = []
+        written = {k: False for k in contribs}
+        pending_id = {k: [j for (j, op) in lst if not isinstance(op, _ConvBR)] for k, lst in contribs.items()}
+        for k, lst in contribs.items():
+            if not lst:
+                raise ValueError("Cell_3d: a step with no selected branch (the reference fails in torch.cat here too)")
+
+        def finalize(k: int) -> None:
+            ids = pending_id[k]
+            while ids:
+                if not written[k]:
+                    if len(ids) >= 2:
+                        steps.append(Add(ids[0], ids[1], k))
+                        del ids[:2]
+                    else:
+                        steps.append(Copy(ids.pop(0), k))
+                    written[k] = True
+                else:
+                    steps.append(Add(k, ids.pop(0), k))
+
+        # Fast path: the conv branches from s0 and from s1 feed the same new states, nothing else does and they share a buffer
+        # (e.g. the all-conv genotype): ONE dual-input launch computes relu(bn(conv(s0))) + relu(bn(conv(s1)))
+        # for all of them, so the running sum never goes through HBM.
+        done = set()
+        a, b = ([(k, op) for k, lst in contribs.items() for (src, op) in lst if src == j and isinstance(op, _ConvBR)] for j in (0, 1))
+        if (a and s0_in_pre and [k for k, _ in a] == [k for k, _ in b] and all(len(contribs[k]) == 2 for k, _ in a)
+                and len({k >= first_cat for k, _ in a}) == 1):
+            steps.append(Dual(tuple(op for _k, op in a), tuple(op for _k, op in b), tuple(k for k, _op in a)))
+            for j, branches in enumerate((a, b)):
+                for k, op in branches:
+                    written[k] = True
+                    done.add((j, id(op)))
+
+        for j in range(n_states):
+            if j >= 2:
+                finalize(j)
+            parts: Dict[Optional[str], list] = {}                        # residual buffer -> [(new state, op, residual state)]
+            for k, lst in contribs.items():
+                for (src, op) in lst:
+                    if src != j or not isinstance(op, _ConvBR) or (j, id(op)) in done:
+                        continue
+                    if written[k]:
+                        res = k                                          # running sum: accumulate in place
+                    else:
+                        ready = [i for i in pending_id[k] if i <= j]     # identity partner already complete
+                        if ready:
+                            pending_id[k].remove(ready[0])
+                        res = ready[0] if ready else None
+                    written[k] = True
+                    parts.setdefault(None if res is None else where[res][0], []).append((k, op, res))
+            for items in parts.values():
+                # all destinations of one launch live in one buffer: a group that spans scratch and concat states splits
+                by_buf: Dict[str, list] = {}
+                for item in items:
+                    by_buf.setdefault(where[item[0]][0], []).append(item)
+                for sub in by_buf.values():
+                    steps.append(Conv(j, tuple(op for (_k, op, _r) in sub), tuple(k for (k, _o, _r) in sub),
+                                      None if sub[0][2] is None else tuple(r for (_k, _o, r) in sub)))
+        for k in contribs:
+            finalize(k)
+        return tuple(steps)
 
     def _fused(self, mods: Sequence[ConvBR_3d]):
         """Concatenated packed weights / scale / shift of sibling convs (cached on their stamps)."""
@@ -473,13 +577,19 @@ class _Cell(nn.Module):
         the same new states, nothing else feeds those, and they share a buffer — else (None, None, False); `whole`: that launch produces
         every new state of the cell, so consumer tails can ride on it.  A property of the genotype and of whether s0 sits in the
         cell's s0|s1 buffer (it went through pre_preprocess, here or as its producer's tail)."""
-        contribs = self._contributions()
-        a, b = ([(k, op) for k, lst in contribs.items() for (src, op) in lst if src == j and isinstance(op, _ConvBR)] for j in (0, 1))
-        first_cat = 2 + self._steps - self.block_multiplier
-        if not (a and s0_in_pre and [k for k, _ in a] == [k for k, _ in b] and all(len(contribs[k]) == 2 for k, _ in a)
-                and len({k >= first_cat for k, _ in a}) == 1):
+        first = self._schedule(s0_in_pre)[0]      # (the schedule decides; a Dual step is always its first)
+        if not isinstance(first, Dual):
             return None, None, False
+        a, b = list(zip(first.dst_states, first.a_mods)), list(zip(first.dst_states, first.b_mods))
         return a, b, len(a) == self._steps and self.block_multiplier == self._steps
+
+    def _one_launch_2d(self, s0, s1, size) -> bool:
+        """A Cell_2d in which every new state is conv(s0) + conv(s1) (the all-conv genotype) can run as ONE launch — the two 1x1
+        ConvBRs and their bilinear resamples in the staging of the dual 3x3 launch (ragmi_cell2d_fwd); s0 / s1 are never written.
+        The shape / dtype / precision half of that condition (the caller knows whether the cell is one dual launch)."""
+        C, (D, H, W) = self.C_out, size
+        return (D == 1 and s0.shape[1] != C and s1.dtype == torch.float32 and s0.dtype == torch.float32
+                and ops.get_conv_precision() == "f16x3" and ops.cell2d_supported(C, s0.shape[1], s1.shape[1], C * self._steps, H, W))
 
     def _run(self, prev_prev_input, prev_input, plan: Optional["_CellPlan"] = None, pre: Optional[torch.Tensor] = None,
              tails: Optional[Sequence["ops.Tail"]] = None):
@@ -493,7 +603,8 @@ class _Cell(nn.Module):
                                       "block_multiplier <= steps (true for every cell the reference builds)")
         s0, s1 = prev_prev_input, prev_input
         pre_has = plan.has if plan is not None else (False, False)
-        a, b, whole = self.dual_branches(pre_has[0] or s0.shape[1] != C)
+        s0_in_pre = pre_has[0] or s0.shape[1] != C
+        a, b, whole = self.dual_branches(s0_in_pre)
         if plan is None:
             plan = _CellPlan(size=self.out_size(s1.shape[2:]), dtype=s1.dtype, has=pre_has, g4=False, dual=whole, store_main=True, tails=False,
                              shared_pre=False, quarter=False)
@@ -502,11 +613,7 @@ class _Cell(nn.Module):
         if not pre_has[0] and s0.shape[1] == C and tuple(s0.shape[2:]) != size:
             s0 = ops.trilinear3d(s0, size, True)     # no pre_preprocess to fuse into (never the case in Network)
         D, H, W = size
-        if (D == 1 and whole and pre is None and not tails and plan.store_main and s0.shape[1] != C and s1.dtype == torch.float32
-                and s0.dtype == torch.float32 and ops.get_conv_precision() == "f16x3"
-                and ops.cell2d_supported(C, s0.shape[1], s1.shape[1], C * self._steps, H, W)):
-            # A Cell_2d in which every new state is conv(s0) + conv(s1) (the all-conv genotype): ONE launch — the two 1x1 ConvBRs and
-            # their bilinear resamples run in the staging of the dual 3x3 launch (ragmi_cell2d_fwd); s0 / s1 are never written
+        if whole and pre is None and not tails and plan.store_main and self._one_launch_2d(s0, s1, size):
             cat = torch.empty((s1.shape[0], self.block_multiplier * C, D, H, W), device=s1.device, dtype=s1.dtype)
             pa, sa, ha = self._fused([op for _k, op in a])
             pb, sb, hb = self._fused([op for _k, op in b])
@@ -517,16 +624,11 @@ class _Cell(nn.Module):
         if pre is None:
             pre = torch.empty((s1.shape[0], 2 * C, D, H, W), device=s1.device, dtype=plan.dtype)
         B, dev, adt = pre.shape[0], pre.device, pre.dtype
-        n_states = 2 + self._steps
-        first_cat = n_states - self.block_multiplier             # first state that lands in the concat buffer
-        contribs = self._contributions()
         cat = (pre if not plan.store_main else   # placeholder pointer: nothing is stored when the output is only consumed by tails
                torch.empty((B, self.block_multiplier * C, D, H, W), device=dev, dtype=adt))
-        scratch = (torch.empty((B, (first_cat - 2) * C, D, H, W), device=dev, dtype=adt)
-                   if first_cat > 2 else None)
+        scratch = (torch.empty((B, (self._steps - self.block_multiplier) * C, D, H, W), device=dev, dtype=adt)
+                   if self.block_multiplier < self._steps else None)
 
-        # (buffer, first channel) of every state
-        where: List[Tuple[torch.Tensor, int]] = []
         # an UP-sampled input runs conv-first through the ConvBR forward (channel mix on the small volume); everything else —
         # down-sampling or an input already at the cell's size — shares one paired launch (measured: splitting an
         # identity + down-sampling pair into two launches costs 43 us instead of 27)
@@ -537,109 +639,44 @@ class _Cell(nn.Module):
             w1, sc1, sh1 = self.preprocess.prepared()
             ops.conv3d_k1_resample_pair([(s0, w0, sc0, sh0, self.pre_preprocess.relu, 0),
                                          (s1, w1, sc1, sh1, self.preprocess.relu, C)], size, pre)
-            where.append((pre, 0))
         else:
-            if pre_has[0]:
-                where.append((pre, 0))             # already written by the producer of prev_prev_input (fused tail)
-            elif s0.shape[1] != C:
+            if not s0_in_pre:
+                s0 = s0.contiguous()
+            elif not pre_has[0]:               # (else: already written by the producer of prev_prev_input, a fused tail)
                 self.pre_preprocess(s0, out=pre, out_ch0=0, resample_to=size)
-                where.append((pre, 0))
-            else:
-                where.append((s0.contiguous(), 0))
             if not pre_has[1]:
                 self.preprocess(s1, out=pre, out_ch0=C, resample_to=size)
-        where.append((pre, C))
-        for k in range(2, n_states):
-            where.append((cat, (k - first_cat) * C) if k >= first_cat else (scratch, (k - 2) * C))
-
-        written = {k: False for k in contribs}
-        pending_id = {k: [j for (j, op) in lst if not isinstance(op, _ConvBR)] for k, lst in contribs.items()}
-        for k, lst in contribs.items():
-            if not lst:
-                raise ValueError("Cell_3d: a step with no selected branch (the reference fails in torch.cat here too)")
-
-        def finalize(k: int) -> None:
-            buf, ch = where[k]
-            ids = pending_id[k]
-            while ids:
-                if not written[k]:
-                    if len(ids) >= 2:
-                        (ba, ca), (bb, cb) = where[ids[0]], where[ids[1]]
-                        ops.add(ba, ca, bb, cb, buf, ch, C)
-                        del ids[:2]
-                    else:
-                        bs, cs = where[ids.pop(0)]
-                        torch.mul(bs[:, cs:cs + C], 1, out=buf[:, ch:ch + C])   # lone identity: a copy KERNEL (no memcpy node when captured)
-                    written[k] = True
-                else:
-                    bs, cs = where[ids.pop(0)]
-                    ops.add(buf, ch, bs, cs, buf, ch, C)
-
-        # Fast path: the conv branches from s0 and from s1 feed the same new states and nothing else does
-        # (e.g. the all-conv genotype): ONE dual-input launch computes relu(bn(conv(s0))) + relu(bn(conv(s1)))
-        # for all of them, so the running sum never goes through HBM.
-        done = set()
-        if a is not None:
-            pa, sa, ha = self._fused([op for _k, op in a])
-            pb, sb, hb = self._fused([op for _k, op in b])
-            groups = [where[k][1] + 4 * g for k, _op in a for g in range(C // 4)]
-            ops.conv3d_k3_dual(pre, C, pa, sa, ha, pb, sb, hb, C * len(a), True, where[a[0][0]][0], groups,
-                               tails=tails, store_main=plan.store_main, x_g4=plan.g4, quarter=plan.quarter)
-            for j, branches in enumerate((a, b)):
-                for k, op in branches:
-                    written[k] = True
-                    done.add((j, id(op)))
-
-        for j in range(n_states):
-            if j >= 2:
-                finalize(j)
-            parts: Dict[object, list] = {}
-            for k, lst in contribs.items():
-                for (src, op) in lst:
-                    if src != j or not isinstance(op, _ConvBR) or (j, id(op)) in done:
-                        continue
-                    if written[k]:
-                        res = where[k]                                   # running sum: accumulate in place
-                    else:
-                        ready = [i for i in pending_id[k] if i <= j]     # identity partner already complete
-                        if ready:
-                            pending_id[k].remove(ready[0])
-                            res = where[ready[0]]
-                        else:
-                            res = None
-                    written[k] = True
-                    parts.setdefault(None if res is None else id(res[0]), []).append((k, op, res))
-            if not parts:
-                continue
-            xbuf, xch = where[j]
-            x = xbuf[:, xch:xch + C]
-            for items in parts.values():
-                mods = [op for (_k, op, _r) in items]
-                packed, scale, shift = self._fused(mods)
-                out_groups, res_groups = [], []
-                for (k, _op, res) in items:
-                    out_groups += [where[k][1] + 4 * g for g in range(C // 4)]
-                    if res is not None:
-                        res_groups += [res[1] + 4 * g for g in range(C // 4)]
-                res_buf = items[0][2][0] if items[0][2] is not None else None
-                # all destinations of one launch live in one buffer except when a scratch state is involved
-                by_buf: Dict[int, list] = {}
-                for idx, (k, _op, _res) in enumerate(items):
-                    by_buf.setdefault(id(where[k][0]), []).append(idx)
-                if len(by_buf) == 1:
-                    ops.conv3d_k3(x, packed, C * len(mods), scale, shift, True, where[items[0][0]][0], out_groups,
-                                  res_buf, res_groups if res_buf is not None else None)
-                else:
-                    for idxs in by_buf.values():
-                        sub = [items[i] for i in idxs]
-                        p2, s2, h2 = self._fused([op for (_k, op, _r) in sub])
-                        og = [where[k][1] + 4 * g for (k, _o, _r) in sub for g in range(C // 4)]
-                        rg = [r[1] + 4 * g for (_k, _o, r) in sub if r is not None for g in range(C // 4)]
-                        ops.conv3d_k3(x, p2, C * len(sub), s2, h2, True, where[sub[0][0]][0], og,
-                                      res_buf, rg if res_buf is not None else None)
-        for k in contribs:
-            finalize(k)
+        self._issue(s0_in_pre, {"pre": pre, "s0": s0, "scratch": scratch, "cat": cat}, plan, tails)
         return cat if plan.store_main else None      # (not stored: the concat existed only inside the kernel, for its tails)
+
+    def _issue(self, s0_in_pre: bool, buffers: Dict[str, Optional[torch.Tensor]], plan: "_CellPlan", tails) -> None:
+        """Launch the schedule on the buffers of _layout: the only place of the cell that launches a 3x3x3 conv or an add (as
+        attributes of `ops` at call time: the benchmark wraps them)."""
+        C, pre = self.C_out, buffers["pre"]
+        where = [(buffers[name], ch) for (name, ch) in self._layout(s0_in_pre)]
+        for step in self._schedule(s0_in_pre):
+            if isinstance(step, Dual):
+                pa, sa, ha = self._fused(step.a_mods)
+                pb, sb, hb = self._fused(step.b_mods)
+                groups = [where[k][1] + 4 * g for k in step.dst_states for g in range(C // 4)]
+                ops.conv3d_k3_dual(pre, C, pa, sa, ha, pb, sb, hb, C * len(step.dst_states), True, where[step.dst_states[0]][0], groups,
+                                   tails=tails, store_main=plan.store_main, x_g4=plan.g4, quarter=plan.quarter)
+            elif isinstance(step, Conv):
+                xbuf, xch = where[step.src]
+                packed, scale, shift = self._fused(step.mods)
+                out_groups = [where[k][1] + 4 * g for k in step.dst_states for g in range(C // 4)]
+                res_buf = res_groups = None
+                if step.res_states is not None:
+                    res_buf = where[step.res_states[0]][0]
+                    res_groups = [where[r][1] + 4 * g for r in step.res_states for g in range(C // 4)]
+                ops.conv3d_k3(xbuf[:, xch:xch + C], packed, C * len(step.mods), scale, shift, True, where[step.dst_states[0]][0], out_groups,
+                              res_buf, res_groups)
+            elif isinstance(step, Add):
+                (ba, ca), (bb, cb), (buf, ch) = where[step.a], where[step.b], where[step.dst]
+                ops.add(ba, ca, bb, cb, buf, ch, C)
+            else:
+                (bs, cs), (buf, ch) = where[step.src], where[step.dst]
+                torch.mul(bs[:, cs:cs + C], 1, out=buf[:, ch:ch + C])   # lone identity: a copy KERNEL (no memcpy node when captured)
 
 
 class Cell_3d(_Cell):
@@ -674,8 +711,12 @@ _CELL3D_ARCH = ((4, 4, 4, 0), (4, 4, 4, 0), (4, 4, 4, 0), (4, 4, 8, -1),
 #   _ChainPlan: sizes[i], cdt[i] (storage type), consumers[i] = ((cell j, role, down), ...) fused onto T[i]'s producer, stored[i] for
 #   i = -2 .. n-1; cells = the _CellPlans; stem0_g4 = T[-2] is G4; stems_fused = both stems as one call (T[-2] never written);
 #   stem_tail_rows = cell 0's pre_preprocess in the idle rows of stem3d1's matrix product.
+#   _HeadPlan (_plan_head; rag_model.py:353-366): level = the last cell's output is at 1/1, 1/2 or 1/4 of the volume; at 1/4: cross_f32 =
+#   last_12_3d is the bf16 -> fp32 crossing launch, chain = last_12_3d and last_6_3d's channel mix as one launch (then the resample + ReLU)
+#   instead of the two units; upconv = upsample_6 + last_3_3d as one kernel.
 _CellPlan = namedtuple("_CellPlan", "size dtype has g4 dual store_main tails shared_pre quarter")
 _ChainPlan = namedtuple("_ChainPlan", "sizes cdt consumers stored cells stem0_g4 stems_fused stem_tail_rows")
+_HeadPlan = namedtuple("_HeadPlan", "level cross_f32 chain upconv")
 
 
 def _down_tail_ok(prod, cons, B, src, dst, src_dt, dst_dt) -> bool:
@@ -799,6 +840,55 @@ def _plan_chain(stem0, stem1, cells, B: int, C_fea: int, vol, adt: torch.dtype, 
             has[j][role] = True
     ro = MappingProxyType
     return _ChainPlan(ro(sizes), ro(cdt), ro(consumers), ro(stored), tuple(plans), stem0_g4, stems_fused, stem_tail_rows)
+
+
+def _plan_head(vol, last_size, last_dtype, m3, m6, m12, train: bool) -> _HeadPlan:
+    """Every decision of the head (rag_model.py:353-366) on a `vol` = (d, h, w) cost volume whose last cell's output has spatial size
+    `last_size` and storage type `last_dtype`.  `train`: a head unit runs its autograd form, which takes none of the fused launches.
+    `m3` None: the caller applies its own last_3_3d (the depth head), no upconv.  Pure, like _plan_chain: reads the units' geometry, the
+    ops switches and the library's host predicates."""
+    d, h, w = (int(v) for v in vol)
+    half = (max(d // 2, 1), h // 2, w // 2)      # (a depth-1 volume, the 2-D networks', keeps its one plane)
+    last_size = tuple(int(v) for v in last_size)
+    if last_size[1] == h:
+        return _HeadPlan(1, False, False, False)
+    if last_size[1] == h // 2:
+        level = 2
+    elif last_size[1] == h // 4:
+        level = 4
+    else:
+        # the reference reaches `return mat` with mat unbound here (UnboundLocalError)
+        raise ValueError("MatchingNet: feature height must be a multiple of 4 (input H a multiple of 12)")
+    # bf16 storage: the head keeps fp32 from its first 1x1x1 conv on (the crossing launch: RAGMI_BF16 | RAGMI_OUT_F32)
+    cross = (level == 4 and last_dtype == torch.bfloat16 and ops.bf16_head_fp32_enabled() and not (train and m12.autograd_mode())
+             and m12._geometry() == 1)
+    # last_12_3d and the channel mix of last_6_3d (conv-first, as ConvBR.forward runs an up-sampling 1x1x1) as ONE launch
+    chain = (level == 4 and not cross and not train and m12._geometry() == 1 and m6._geometry() == 1 and ops.chain_k1_enabled()
+             and _volume(half) > _volume(last_size) and m6.conv.out_channels <= m6.conv.in_channels
+             and ops.conv3d_k1_chain_supported(m12.conv.in_channels, m12.conv.out_channels, m6.conv.out_channels))
+    # upsample_6 + last_3_3d as ONE kernel when the upsampling is an exact factor 2 (always, for the sizes the reference accepts)
+    upconv = (m3 is not None and not train and m3._small() and m3.conv.out_channels == 1 and (level == 4 or last_size == half)
+              and (d, h, w) == tuple(2 * v for v in half) and ops.upconv3d_c1_supported(m6.conv.out_channels, *half))
+    return _HeadPlan(level, bool(cross), bool(chain), bool(upconv))
+
+
+def _head_quarter(last5, m12, m6, half, plan: _HeadPlan) -> torch.Tensor:
+    """The head's 1/4-level step, last_6_3d(upsample_12(last_12_3d(last5))) at `half` (upsample_12 is fused into last_6_3d's 1x1x1
+    kernel, conv-first), launched as `plan` says; shared by MatchingNet._head and depth.Network._trunk."""
+    B, dev = last5.shape[0], last5.device
+    if plan.chain:
+        w1, s1, h1 = m12.prepared()
+        w2, s2, h2 = m6.prepared()
+        low = torch.empty((B, m6.conv.out_channels) + tuple(last5.shape[2:]), device=dev, dtype=last5.dtype)
+        ops.conv3d_k1_chain(last5, w1, s1, h1, m12.relu, w2, s2, h2, False, low)
+        y = torch.empty((B, m6.conv.out_channels) + tuple(half), device=dev, dtype=last5.dtype)
+        ops.trilinear3d_act(low, half, True, m6.relu, y, 0)
+        return y
+    if plan.cross_f32:
+        y12 = m12(last5, out=torch.empty((B, m12.conv.out_channels) + tuple(last5.shape[2:]), device=dev, dtype=torch.float32))
+    else:
+        y12 = m12(last5)
+    return m6(y12, resample_to=half)
 
 
 class MatchingNet(nn.Module):
@@ -964,55 +1054,23 @@ class MatchingNet(nn.Module):
         return T[n - 1]
 
     def _head(self, vol, last_output, i3, i6, i12):
-        d, h, w = vol
+        """last_12_3d / last_6_3d / last_3_3d and their upsamples (rag_model.py:353-366): `_plan_head` decides, this allocates and launches."""
+        m3, m6, m12 = self.last_3_3d[i3], self.last_6_3d[i6], self.last_12_3d[i12]
+        train = any(m.autograd_mode(last_output) for m in (m3, m6, m12))
+        plan = _plan_head(vol, last_output.shape[2:], last_output.dtype, m3, m6, m12, train)
         # `mat` — the [B,1,d,h,w] cost the soft-argmin reads — is always stored in fp32, also under bf16 activation storage: with
         # |cost| ~ 1e4 a bf16 rounding of it alone moved the disparity by 0.04-0.09 px (tests/analysis_bf16_stage_epe.py), and the
         # tensor is 1/12 of one level-3 activation
         f32 = torch.float32
-        if last_output.size()[3] == h:
-            return self.last_3_3d[i3](last_output, out_dtype=f32)
-        heads = (self.last_3_3d[i3], self.last_6_3d[i6], self.last_12_3d[i12])
-        up = ag.resample if any(m.autograd_mode(last_output) for m in heads) else ops.trilinear3d
-        def up_last3(y):
-            """upsample_6 + last_3_3d (rag_model.py:357-365): ONE kernel when the upsampling is an exact factor 2 (always, for the
-            sizes the reference accepts) — the 12-channel full-resolution tensor is never written."""
-            m3 = self.last_3_3d[i3]
-            if (up is ops.trilinear3d and m3._small() and m3.conv.out_channels == 1 and tuple(y.shape[2:]) == (d // 2, h // 2, w // 2)
-                    and (d, h, w) == (2 * (d // 2), 2 * (h // 2), 2 * (w // 2)) and ops.upconv3d_c1_supported(y.shape[1], d // 2, h // 2, w // 2)):
-                wk, scale, shift = m3.prepared()             # the raw [1, C, 3, 3, 3] weight (VALU forms read it as is)
-                return ops.upconv3d_c1(y, wk, scale, shift, m3.relu, out_dtype=f32)
-            return m3(up(y, (d, h, w), True), out_dtype=f32)
-
-        if last_output.size()[3] == h // 2:
-            return up_last3(self.last_6_3d[i6](last_output))
-        if last_output.size()[3] == h // 4:
-            # upsample_12 is fused into last_6_3d's 1x1x1 kernel (conv-first); upsample_6 is fused into last_3_3d's kernel
-            m12 = self.last_12_3d[i12]
-            if (last_output.dtype == torch.bfloat16 and ops.bf16_head_fp32_enabled() and not m12.autograd_mode(last_output)
-                    and m12._geometry() == 1):
-                # bf16 storage: the head keeps fp32 from its first 1x1x1 conv on (the crossing launch: RAGMI_BF16 | RAGMI_OUT_F32)
-                y12 = m12(last_output, out=torch.empty((last_output.shape[0], m12.conv.out_channels) + tuple(last_output.shape[2:]),
-                                                       device=last_output.device, dtype=f32))
-            else:
-                m6 = self.last_6_3d[i6]
-                half = (d // 2, h // 2, w // 2)
-                if (up is ops.trilinear3d and m12._geometry() == 1 and m6._geometry() == 1 and ops.chain_k1_enabled()
-                        and _volume(half) > _volume(last_output.shape[2:]) and m6.conv.out_channels <= m6.conv.in_channels
-                        and ops.conv3d_k1_chain_supported(m12.conv.in_channels, m12.conv.out_channels, m6.conv.out_channels)):
-                    # last_12_3d and the channel mix of last_6_3d (conv-first, as ConvBR.forward runs an up-sampling 1x1x1) as ONE launch
-                    w1, s1, h1 = m12.prepared()
-                    w2, s2, h2 = m6.prepared()
-                    low = torch.empty((last_output.shape[0], m6.conv.out_channels) + tuple(last_output.shape[2:]), device=last_output.device,
-                                      dtype=last_output.dtype)
-                    ops.conv3d_k1_chain(last_output, w1, s1, h1, m12.relu, w2, s2, h2, False, low)
-                    y = torch.empty((last_output.shape[0], m6.conv.out_channels) + half, device=last_output.device, dtype=last_output.dtype)
-                    ops.trilinear3d_act(low, half, True, m6.relu, y, 0)
-                    return up_last3(y)
-                y12 = m12(last_output)
-            y = self.last_6_3d[i6](y12, resample_to=(d // 2, h // 2, w // 2))
-            return up_last3(y)
-        # the reference reaches `return mat` with mat unbound here (UnboundLocalError)
-        raise ValueError("MatchingNet: feature height must be a multiple of 4 (input H a multiple of 12)")
+        if plan.level == 1:
+            return m3(last_output, out_dtype=f32)
+        d, h, w = vol
+        y = m6(last_output) if plan.level == 2 else _head_quarter(last_output, m12, m6, (d // 2, h // 2, w // 2), plan)
+        if plan.upconv:         # the 12-channel full-resolution tensor is never written
+            wk, scale, shift = m3.prepared()             # the raw [1, C, 3, 3, 3] weight (VALU forms read it as is)
+            return ops.upconv3d_c1(y, wk, scale, shift, m3.relu, out_dtype=f32)
+        up = ag.resample if train else ops.trilinear3d
+        return m3(up(y, (d, h, w), True), out_dtype=f32)
 
     def cost_volume(self, left_fea, right_fea):
         """The inline loop of rag_model.py:375-383 as one kernel."""

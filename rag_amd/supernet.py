@@ -27,7 +27,8 @@ import torch.nn.functional as F
 from . import autograd as ag
 from . import ops
 from .depth import FP32_ONLY, MAX_DEPTH, DepthHeadFn, DispHead
-from .modules import (OPS_2d, OPS_3d, PRIMITIVES, PRIMITIVES_3D, ConvBR_2d, ConvBR_3d, Disp, Genotype, MatchingNet, _ConvBR)
+from .modules import (OPS_2d, OPS_3d, PRIMITIVES, PRIMITIVES_3D, ConvBR_2d, ConvBR_3d, Disp, Genotype, MatchingNet, _ConvBR,
+                      _scale_dimension)
 
 
 def _resize(x: torch.Tensor, size: Sequence[int]) -> torch.Tensor:
@@ -112,7 +113,7 @@ class _SuperCell(nn.Module):
 
     def scale_dimension(self, dim, scale):
         assert isinstance(dim, int)
-        return int((float(dim) - 1.0) * scale + 1.0) if dim % 2 else int(dim * scale)
+        return _scale_dimension(dim, scale)
 
     def prev_feature_resize(self, prev_feature, mode):
         scale = 0.5 if mode == "down" else 2

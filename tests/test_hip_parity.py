@@ -541,6 +541,36 @@ def test_cell3d_golden(ra, name):
     np.testing.assert_allclose(cat.cpu().numpy(), g[f"{name}::out"], **TOL)
 
 
+@pytest.mark.parametrize("rows", [O.ALL_CONV, np.array([[0, 1], [1, 0], [3, 0], [2, 1], [8, 1], [6, 0]]), O.ALL_SKIP],
+                         ids=["conv", "mixed", "skip"])
+def test_cell3d_block_multiplier_below_steps(ra, rows):
+    """block_multiplier 2 < steps 3: state 2 lives in a scratch buffer, only states 3 and 4 are concatenated, and a launch whose
+    destinations span both buffers splits.  Against the torch composition over _contributions() on the same parameters (CPU, fp64)."""
+    torch.manual_seed(17)
+    cell = ra.Cell_3d(3, 2, 4, 4, ra.Genotype(rows, None, rows, None), 4, 0).eval()
+    with torch.no_grad():
+        for m in cell.modules():
+            if isinstance(m, torch.nn.BatchNorm3d):
+                m.running_mean.normal_(0, 0.1); m.running_var.uniform_(0.5, 1.5); m.weight.uniform_(0.5, 1.5); m.bias.normal_(0, 0.1)
+        x0, x1 = torch.randn((1, 8, 4, 12, 20)), torch.randn((1, 8, 4, 12, 20))
+
+        def cbr(mod, z, k):
+            w, bn = mod.conv.weight.double(), mod.bn
+            y = F.batch_norm(F.conv3d(z, w, padding=(k - 1) // 2), bn.running_mean.double(), bn.running_var.double(), bn.weight.double(),
+                             bn.bias.double(), eps=bn.eps)
+            return F.relu(y)
+        st = [cbr(cell.pre_preprocess, x0.double(), 1), cbr(cell.preprocess, x1.double(), 1)]
+        contribs = cell._contributions()
+        for k in sorted(contribs):
+            st.append(sum(cbr(op, st[j], 3) if isinstance(op, ra.ConvBR_3d) else st[j] for (j, op) in contribs[k]))
+        want = torch.cat(st[-2:], 1)
+        cell = cell.to(DEV)
+        s1 = gpu(x1)
+        prev, cat = cell(gpu(x0), s1)
+    assert prev is s1 and tuple(cat.shape) == (1, 8, 4, 12, 20)
+    np.testing.assert_allclose(cat.cpu().numpy(), want.numpy(), **TOL)
+
+
 # --------------------------------------------------------------------------- MatchingNet end to end
 def _net_from_golden(ra, g, maxdisp):
     rows = g["rows"]

@@ -457,6 +457,214 @@ def test_chain_plan_dual_cells_by_genotype(built_lib, rows, any_dual, dtype):
         _switches(ops)
 
 
+# ---- a cell's launches as data (rag_amd.modules._Cell._schedule) and the head's decisions (_plan_head): checked without a GPU.
+UNSORTED_ROWS = np.array([[1, 1], [0, 0], [4, 1], [2, 0], [7, 1], [8, 1]])   # (the second unsorted set of the pairing test above)
+NAMED_ROWS = {"conv": O.ALL_CONV, "skip": O.ALL_SKIP, "mixed": MIXED_ROWS, "unsorted": UNSORTED_ROWS}
+
+
+def _cell(rows, steps=3, block_multiplier=3):
+    import rag_amd
+    return rag_amd.Cell_3d(steps, block_multiplier, 4, 4, rag_amd.Genotype(rows, None, rows, None), 4, 0)
+
+
+def test_cell_schedule_named_genotypes():
+    """The schedules of the four named row sets, written out by hand from the executor's loop (sources in ascending order; a conv takes
+    its target's running sum, else an identity partner that is already complete, as its residual; identities left over are added when
+    their target is first read and at the end)."""
+    from rag_amd.modules import Add, Conv, Dual
+    c = _cell(O.ALL_CONV)
+    o = c._ops
+    assert c._schedule(True) == (Dual((o[0], o[2], o[4]), (o[1], o[3], o[5]), (2, 3, 4)),)
+    # s0 outside the s0|s1 buffer: no dual launch; the three convs of s0 stacked, then those of s1 onto their running sums
+    assert c._schedule(False) == (Conv(0, (o[0], o[2], o[4]), (2, 3, 4), None), Conv(1, (o[1], o[3], o[5]), (2, 3, 4), (2, 3, 4)))
+    c = _cell(O.ALL_SKIP)
+    for s0_in_pre in (True, False):
+        sched = c._schedule(s0_in_pre)
+        assert sched == (Add(0, 1, 2), Add(0, 1, 3), Add(0, 1, 4))
+        assert not any(isinstance(s, (Conv, Dual)) for s in sched)
+    # MIXED_ROWS: state 2 = conv(s0) + s1, state 3 = s0 + conv(s1), state 4 = conv(s1) + state 3 (ops paired by position)
+    c = _cell(MIXED_ROWS)
+    o = c._ops
+    for s0_in_pre in (True, False):
+        assert c._schedule(s0_in_pre) == (Conv(0, (o[0],), (2,), None), Conv(1, (o[3],), (3,), (0,)), Conv(1, (o[4],), (4,), None),
+                                          Add(2, 1, 2), Add(4, 3, 4))
+    # UNSORTED_ROWS: state 2 = conv(s0) + s1, state 3 = conv(s0) + state 2, state 4 = conv(state 2) + conv(state 3)
+    c = _cell(UNSORTED_ROWS)
+    o = c._ops
+    for s0_in_pre in (True, False):
+        assert c._schedule(s0_in_pre) == (Conv(0, (o[0], o[2]), (2, 3), None), Add(2, 1, 2), Conv(2, (o[4],), (4,), None), Add(3, 2, 3),
+                                          Conv(3, (o[5],), (4,), (4,)))
+
+
+def _random_rows(rng, steps=3):
+    """each step selects one or two of its incoming edges, each with a random primitive; the rows in random order"""
+    rows, offset = [], 0
+    for i in range(steps):
+        for e in rng.choice(2 + i, size=rng.integers(1, 3), replace=False):
+            rows.append([offset + int(e), int(rng.integers(0, 2))])
+        offset += 2 + i
+    return np.array(rows)[rng.permutation(len(rows))]
+
+
+def _schedule_row_sets():
+    rng = np.random.default_rng(20240611)
+    return list(NAMED_ROWS.items()) + [(f"random{i}", _random_rows(rng)) for i in range(200)]
+
+
+def _interpret_schedule(cell, s0_in_pre, s0, s1):
+    """Run the schedule on fp64 CPU tensors, one per state, checking on the way that no state is read before its last writer and that
+    one launch keeps to one destination buffer and one residual buffer.  Returns (states, the (source, op) pairs the steps applied)."""
+    import torch.nn.functional as F
+    from rag_amd.modules import Add, Conv, Copy, Dual
+    sched, where = cell._schedule(s0_in_pre), cell._layout(s0_in_pre)
+    assert len(set(where)) == len(where) and where[0] == (("pre", 0) if s0_in_pre else ("s0", 0)) and where[1] == ("pre", cell.C_out)
+
+    def writes(step):
+        return step.dst_states if isinstance(step, (Dual, Conv)) else (step.dst,)
+
+    left = {k: sum(k in writes(s) for s in sched) for k in range(2 + cell._steps)}      # writers still to come
+    states, applied = {0: s0, 1: s1}, []
+
+    def cbr(m, x):
+        return F.relu(F.batch_norm(F.conv3d(x, m.conv.weight, padding=1), m.bn.running_mean, m.bn.running_var, m.bn.weight, m.bn.bias))
+
+    def read(k, step):
+        assert left[k] == 0 or k in writes(step), f"state {k} read by {step} before its last writer"
+        return states[k]
+
+    for step in sched:
+        if isinstance(step, Dual):
+            new = {k: cbr(ma, read(0, step)) + cbr(mb, read(1, step)) for k, ma, mb in zip(step.dst_states, step.a_mods, step.b_mods)}
+            applied += [(0, m) for m in step.a_mods] + [(1, m) for m in step.b_mods]
+        elif isinstance(step, Conv):
+            assert len({where[k][0] for k in step.dst_states}) == 1
+            assert step.res_states is None or (len(step.res_states) == len(step.dst_states) and len({where[r][0] for r in step.res_states}) == 1)
+            new = {}
+            for i, (k, m) in enumerate(zip(step.dst_states, step.mods)):
+                new[k] = cbr(m, read(step.src, step))
+                applied.append((step.src, m))
+                if step.res_states is not None:
+                    r = step.res_states[i]
+                    assert r == k or r not in step.dst_states
+                    new[k] = new[k] + read(r, step)
+                    applied += [] if r == k else [(r, "identity", k)]
+        elif isinstance(step, Add):
+            new = {step.dst: read(step.a, step) + read(step.b, step)}
+            applied += [(j, "identity", step.dst) for j in (step.a, step.b) if j != step.dst]
+        else:
+            assert isinstance(step, Copy)
+            new = {step.dst: read(step.src, step).clone()}
+            applied.append((step.src, "identity", step.dst))
+        states.update(new)
+        for k in new:
+            left[k] -= 1
+    return states, applied
+
+
+_SCHEDULE_SETS = _schedule_row_sets()
+
+
+@pytest.mark.parametrize("steps,block_multiplier", [(3, 3), (3, 2), (3, 1)])
+@pytest.mark.parametrize("s0_in_pre", [True, False])
+def test_cell_schedule_interpreted_matches_contributions(steps, block_multiplier, s0_in_pre):
+    """Every concat state the schedule produces == sum over _contributions()[k] of op(state_j) (fp64, 1e-12 relative), for the named row
+    sets and 200 seeded random ones; every (source, op) of _contributions() is applied by exactly one step."""
+    import torch.nn.functional as F
+    from rag_amd.modules import _ConvBR
+    gen = torch.Generator().manual_seed(11)
+    for name, rows in _SCHEDULE_SETS:
+        cell = _cell(rows, steps, block_multiplier).double().eval()
+        for m in cell._ops:
+            if isinstance(m, _ConvBR):
+                m.bn.running_mean.copy_(torch.randn(4, generator=gen, dtype=torch.float64) * 0.1)
+                m.bn.running_var.copy_(torch.rand(4, generator=gen, dtype=torch.float64) + 0.5)
+        s0, s1 = (torch.randn((1, 4, 2, 3, 4), generator=gen, dtype=torch.float64) for _ in range(2))
+        with torch.no_grad():
+            got, applied = _interpret_schedule(cell, s0_in_pre, s0, s1)
+            contribs = cell._contributions()
+            want = {0: s0, 1: s1}
+            for k in sorted(contribs):
+                want[k] = sum(F.relu(F.batch_norm(F.conv3d(want[j], op.conv.weight, padding=1), op.bn.running_mean, op.bn.running_var,
+                                                  op.bn.weight, op.bn.bias)) if isinstance(op, _ConvBR) else want[j] for (j, op) in contribs[k])
+        expected = sorted((j, id(op)) if isinstance(op, _ConvBR) else (j, -1, k) for k, lst in contribs.items() for (j, op) in lst)
+        assert sorted((a[0], id(a[1])) if len(a) == 2 else (a[0], -1, a[2]) for a in applied) == expected, (name, rows)
+        for k in range(2 + steps - block_multiplier, 2 + steps):
+            err = float((got[k] - want[k]).abs().max()) / float(want[k].abs().max())
+            assert err <= 1e-12, (name, rows, k, err)
+
+
+@pytest.mark.parametrize("rows,any_dual", [(O.ALL_CONV, True), (O.ALL_SKIP, False), (MIXED_ROWS, False)])
+def test_cell_schedule_is_cached_and_dual_branches_reads_it(rows, any_dual):
+    import rag_amd
+    from rag_amd.modules import Dual, _ConvBR
+    net = rag_amd.MatchingNet(rag_amd.Genotype(rows, None, rows, None), maxdisp=48).eval()
+    keys = set(net.state_dict())
+    for c in (u[0] for u in net.cells_3d):
+        contribs = c._contributions()
+        assert c._contributions() is contribs
+        expect = all([src for src, _op in lst] == [0, 1] and all(isinstance(op, _ConvBR) for _s, op in lst) for lst in contribs.values())
+        for s0_in_pre in (True, False):
+            sched = c._schedule(s0_in_pre)
+            assert c._schedule(s0_in_pre) is sched and isinstance(sched, tuple)
+            a, b, whole = c.dual_branches(s0_in_pre)
+            if isinstance(sched[0], Dual):
+                assert a == list(zip(sched[0].dst_states, sched[0].a_mods)) and b == list(zip(sched[0].dst_states, sched[0].b_mods))
+            else:
+                assert (a, b, whole) == (None, None, False)
+            assert not any(isinstance(s, Dual) for s in sched[1:])
+            assert whole == (expect and s0_in_pre) and expect == any_dual
+    assert set(net.state_dict()) == keys and not any("cache" in n for n, _m in net.named_modules())      # the caches stay out of the tree
+
+
+def test_plan_head_levels_switches_and_training(built_lib):
+    import rag_amd
+    from rag_amd import ops
+    from rag_amd.modules import _HeadPlan, _plan_head
+    net = rag_amd.MatchingNet(rag_amd.ALL_CONV_GENOTYPE, maxdisp=48).eval()
+    m3, m6, m12 = net.last_3_3d[0], net.last_6_3d[0], net.last_12_3d[0]
+    vol, f32, bf16 = (16, 48, 72), torch.float32, torch.bfloat16
+    sizes = {1: (16, 48, 72), 2: (8, 24, 36), 4: (4, 12, 18)}
+    chain = bool(built_lib.ragmi_conv3d_k1_chain_supported(48, 24, 12))
+    upconv = bool(built_lib.ragmi_upconv3d_c1_supported(12, 8, 24, 36))
+    old = ops.chain_k1_enabled(), ops.bf16_head_fp32_enabled()
+
+    def plan(level, dtype=f32, train=False, vol=vol):
+        return _plan_head(vol, sizes[level], dtype, m3, m6, m12, train)
+
+    try:
+        ops.set_chain_k1(True)
+        ops.set_bf16_head_fp32(True)
+        with torch.no_grad():
+            for dtype in (f32, bf16):
+                assert plan(1, dtype) == _HeadPlan(1, False, False, False)
+                assert plan(2, dtype) == _HeadPlan(2, False, False, upconv)
+            assert plan(4) == _HeadPlan(4, False, chain, upconv)
+            assert plan(4, bf16) == _HeadPlan(4, True, False, upconv)
+            ops.set_bf16_head_fp32(False)
+            assert plan(4, bf16) == _HeadPlan(4, False, chain, upconv)
+            ops.set_chain_k1(False)
+            assert plan(4) == plan(4, bf16) == _HeadPlan(4, False, False, upconv)
+            ops.set_chain_k1(True)
+            ops.set_bf16_head_fp32(True)
+            # an odd d: the upsampling is no exact factor 2
+            assert plan(4, vol=(17, 48, 72)) == _HeadPlan(4, False, chain, False)
+            assert plan(2, vol=(17, 48, 72)) == _HeadPlan(2, False, False, False)
+            # a unit in its autograd form takes none of the fused launches
+            for level in (2, 4):
+                p = plan(level, train=True)
+                assert (p.level, p.chain, p.upconv) == (level, False, False)
+            with pytest.raises(ValueError, match="feature height must be a multiple of 4"):
+                _plan_head(vol, (5, 16, 24), f32, m3, m6, m12, False)
+            # the depth network's call: 2-D units on a depth-1 volume, its own last_3_3d (no m3)
+            n6, n12 = rag_amd.ConvBR_2d(24, 12, 1, 1, 0).eval(), rag_amd.ConvBR_2d(48, 24, 1, 1, 0).eval()
+            assert _plan_head((1, 48, 72), (1, 12, 18), f32, None, n6, n12, False) == _HeadPlan(4, False, chain, False)
+            ops.set_chain_k1(False)
+            assert _plan_head((1, 48, 72), (1, 12, 18), f32, None, n6, n12, False) == _HeadPlan(4, False, False, False)
+    finally:
+        ops.set_chain_k1(old[0])
+        ops.set_bf16_head_fp32(old[1])
+
+
 # ---- which kernel a 3x3x3 call runs on is decided once in the library (k3_route, rag_amd/csrc/conv3d.hip); the four shape predicates
 # the fused executor plans from all ask it, so their answers cannot contradict each other.
 def _csrc_constant(name):
