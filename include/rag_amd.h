@@ -553,6 +553,14 @@ int ragmi_disparity_regression_bwd(const void* dout, void* dprob, int B, int D, 
 int ragmi_stereo_metrics_fwd(const void* disp_est, const void* disp_gt, int B, int H, int W, float maxdisp, void* acc, void* out,
                              void* stream);
 
+/* The same three launches, and the epoch's meter (AverageMeterDict of utilstool/experiment.py:126-151, which the reference feeds
+ * with six .item() floats per batch, rag.py:386-396, 457-466) updated in the finalize kernel: after storing out[0..7] its one
+ * thread adds, in double, meter[k] += (double)out[k] for k < 6 (the stored floats, as the reference sums Python floats; a NaN
+ * loss propagates), meter[6] += 1 (batches) and meter[7] += out[7] (images kept).  meter: 8 doubles on the device, zeroed by the
+ * caller at the start of an epoch; no atomics, no memset, no extra launch.  out is bit for bit ragmi_stereo_metrics_fwd's. */
+int ragmi_stereo_metrics_meter_fwd(const void* disp_est, const void* disp_gt, int B, int H, int W, float maxdisp, void* acc, void* out,
+                                   void* meter, void* stream);
+
 /* gradient of out[0] w.r.t. disp_est: ddisp = gout[0] * [mask] * clamp(est - gt, -1, 1) / out[6] */
 int ragmi_masked_smooth_l1_bwd(const void* disp_est, const void* disp_gt, const void* out, const void* gout, void* ddisp,
                                int B, int H, int W, float maxdisp, void* stream);

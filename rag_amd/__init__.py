@@ -12,6 +12,8 @@ from . import ops  # noqa: F401
 from . import autograd  # noqa: F401
 from . import metrics  # noqa: F401
 from . import train  # noqa: F401
+from .metrics import EpochMeter  # noqa: F401
+from .train import search_eval_step  # noqa: F401
 from .modules import (  # noqa: F401
     ALL_CONV_GENOTYPE, ALL_SKIP_GENOTYPE, Cell_3d, ConvBR_3d, Disp, DisparityRegression, Genotype,
     Identity_3d, MatchingNet, OPS_3d, PRIMITIVES_3D,
@@ -29,6 +31,7 @@ from . import data  # noqa: E402,F401
 from .data import color_stats, lanczos_taps, prepare_batch, random_crop_origin, resize_lanczos, resize_lanczos_torch, transfer_color  # noqa: E402,F401
 
 __all__ = [
+    "EpochMeter", "search_eval_step",
     "Network", "Cell_2d", "ConvBR_2d", "DepthNetwork", "load_depth_checkpoint",
     "data", "prepare_batch", "random_crop_origin", "color_stats", "transfer_color", "lanczos_taps", "resize_lanczos", "resize_lanczos_torch",
     "ops", "load_library", "lib_path", "MatchingNet", "Cell_3d", "ConvBR_3d", "Identity_3d", "Disp",

@@ -49,7 +49,10 @@ __global__ __launch_bounds__(256) void stereo_metrics_kernel(const float* __rest
 }
 
 // out[0..5] = loss, EPE, D1, Thres1, Thres2, Thres3;  out[6] = number of masked pixels in the batch;  out[7] = images kept
-__global__ void stereo_metrics_finalize_kernel(const float* __restrict__ acc, int B, float* __restrict__ out) {
+// meter (may be null): the epoch's AverageMeterDict (utilstool/experiment.py:126-151) as 8 doubles, updated by this one thread:
+// meter[0..5] += the six floats just stored (the reference sums the .item() floats in Python doubles; a NaN loss propagates as
+// there), meter[6] += 1 (batches), meter[7] += images kept.
+__global__ void stereo_metrics_finalize_kernel(const float* __restrict__ acc, int B, float* __restrict__ out, double* __restrict__ meter) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double n_all = 0.0, l_all = 0.0, m[5] = {0, 0, 0, 0, 0};
   int kept = 0;
@@ -67,6 +70,11 @@ __global__ void stereo_metrics_finalize_kernel(const float* __restrict__ acc, in
   for (int k = 0; k < 5; ++k) out[1 + k] = kept ? (float)(m[k] / kept) : 0.f;
   out[6] = (float)n_all;
   out[7] = (float)kept;
+  if (meter) {
+    for (int k = 0; k < 6; ++k) meter[k] += (double)out[k];
+    meter[6] += 1.0;
+    meter[7] += (double)out[7];
+  }
 }
 
 // d loss / d est = gout * [mask] * clamp(est - gt, -1, 1) / n_mask   (n_mask = out[6] of the forward)
@@ -81,13 +89,9 @@ __global__ __launch_bounds__(256) void masked_smooth_l1_bwd_kernel(const float* 
   dest[i] = r;
 }
 
-}  // namespace ragmi
-
-extern "C" int ragmi_stereo_metrics_fwd(const void* disp_est, const void* disp_gt, int B, int H, int W, float maxdisp, void* acc,
-                                        void* out, void* stream) {
-  using namespace ragmi;
-  RAGMI_REQUIRE(disp_est && disp_gt && acc && out, RAGMI_EINVAL, "stereo_metrics: null pointer");
-  RAGMI_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535, RAGMI_EINVAL, "stereo_metrics: bad size");
+// the three launches of both entry points; `meter` null: the finalize kernel stores `out` only
+static int stereo_metrics_launch(const void* disp_est, const void* disp_gt, int B, int H, int W, float maxdisp, void* acc, void* out,
+                                 void* meter, void* stream) {
   const int64_t hw = (int64_t)H * W;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // zeroed by a kernel, not hipMemsetAsync: memset / memcpy nodes of a captured hipGraph are corrupted by memcpys issued on the null
@@ -96,8 +100,26 @@ extern "C" int ragmi_stereo_metrics_fwd(const void* disp_est, const void* disp_g
   const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(hw, 1024), 64));
   hipLaunchKernelGGL(stereo_metrics_kernel, dim3(gx, B), dim3(256), 0, st, (const float*)disp_est, (const float*)disp_gt, hw, maxdisp,
                      (float*)acc);
-  hipLaunchKernelGGL(stereo_metrics_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)acc, B, (float*)out);
+  hipLaunchKernelGGL(stereo_metrics_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)acc, B, (float*)out, (double*)meter);
   return check_launch("stereo_metrics");
+}
+
+}  // namespace ragmi
+
+extern "C" int ragmi_stereo_metrics_fwd(const void* disp_est, const void* disp_gt, int B, int H, int W, float maxdisp, void* acc,
+                                        void* out, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(disp_est && disp_gt && acc && out, RAGMI_EINVAL, "stereo_metrics: null pointer");
+  RAGMI_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535, RAGMI_EINVAL, "stereo_metrics: bad size");
+  return stereo_metrics_launch(disp_est, disp_gt, B, H, W, maxdisp, acc, out, nullptr, stream);
+}
+
+extern "C" int ragmi_stereo_metrics_meter_fwd(const void* disp_est, const void* disp_gt, int B, int H, int W, float maxdisp, void* acc,
+                                              void* out, void* meter, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(disp_est && disp_gt && acc && out && meter, RAGMI_EINVAL, "stereo_metrics_meter: null pointer");
+  RAGMI_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535, RAGMI_EINVAL, "stereo_metrics_meter: bad size");
+  return stereo_metrics_launch(disp_est, disp_gt, B, H, W, maxdisp, acc, out, meter, stream);
 }
 
 extern "C" int ragmi_masked_smooth_l1_bwd(const void* disp_est, const void* disp_gt, const void* out, const void* gout, void* ddisp,

@@ -8,7 +8,7 @@ training loss never leaves the device.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -18,16 +18,49 @@ from ._lib import check, load_library
 NAMES = ("loss", "EPE", "D1", "Thres1", "Thres2", "Thres3")
 
 
-def _raw(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float) -> torch.Tensor:
+class EpochMeter:
+    """The `AverageMeterDict` of one epoch (utilstool/experiment.py:126-151) on the device.  The reference feeds it with six
+    `.item()` synchronisations per batch (rag.py:386-396, 457-466); here the finalize kernel of the loss / metrics launch adds the
+    batch's floats to `sums` (ragmi_stereo_metrics_meter_fwd: no extra launch, nothing leaves the device) and `mean()` is the
+    epoch's one device-to-host copy.
+
+    `sums`: float64 [8] - running sums of loss, EPE, D1, Thres1, Thres2, Thres3 (each batch's float added in double, as the
+    reference adds Python floats), the number of batches, the images kept.  `last`: the most recent batch's 8-float vector (the
+    kernel's `out` itself, not a copy; None before the first batch)."""
+
+    def __init__(self, device):
+        self.sums = torch.zeros((8,), device=device, dtype=torch.float64)
+        self.last = None
+
+    def reset(self) -> None:
+        self.sums.zero_()
+        self.last = None
+
+    def mean(self) -> Dict[str, float]:
+        """AverageMeterDict.mean(): NAMES -> sums[k] / sums[6] as Python floats (nan before the first batch)."""
+        vals = self.sums.tolist()          # the only synchronisation
+        n = vals[6]
+        return {k: (v / n if n else float("nan")) for k, v in zip(NAMES, vals[:6])}
+
+
+def _raw(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float, meter: Optional[EpochMeter] = None) -> torch.Tensor:
     ops._need_gpu(disp_est, disp_gt)
     if disp_est.shape != disp_gt.shape or disp_est.dim() != 3:
         raise ValueError("stereo metrics: disp_est and disp_gt must both be [B, H, W]")   # metrics.py:14-18
     est, gt = disp_est.contiguous(), disp_gt.contiguous()
     B, H, W = est.shape
     buf = torch.empty((B + 1, 8), device=est.device, dtype=torch.float32)
-    check(load_library().ragmi_stereo_metrics_fwd(est.data_ptr(), gt.data_ptr(), B, H, W, float(maxdisp), buf.data_ptr(),
-                                                  buf[B].data_ptr(), ops._stream()), "stereo_metrics")
-    return buf[B]
+    out = buf[B]
+    if meter is None:
+        check(load_library().ragmi_stereo_metrics_fwd(est.data_ptr(), gt.data_ptr(), B, H, W, float(maxdisp), buf.data_ptr(),
+                                                      out.data_ptr(), ops._stream()), "stereo_metrics")
+        return out
+    if not isinstance(meter, EpochMeter) or meter.sums.device != est.device:
+        raise ValueError("stereo metrics: meter must be a rag_amd.metrics.EpochMeter on the device of disp_est")
+    check(load_library().ragmi_stereo_metrics_meter_fwd(est.data_ptr(), gt.data_ptr(), B, H, W, float(maxdisp), buf.data_ptr(),
+                                                        out.data_ptr(), meter.sums.data_ptr(), ops._stream()), "stereo_metrics_meter")
+    meter.last = out
+    return out
 
 
 class StereoMetrics:
@@ -45,10 +78,11 @@ class StereoMetrics:
         return dict(zip(NAMES, vals[:6]))
 
 
-def stereo_metrics(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float = 192) -> StereoMetrics:
-    """loss, EPE, D1, Thres1/2/3 of Appr.eval (rag.py:418-430) for disp_est, disp_gt [B,H,W]; no gradient."""
+def stereo_metrics(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float = 192, meter: Optional[EpochMeter] = None) -> StereoMetrics:
+    """loss, EPE, D1, Thres1/2/3 of Appr.eval (rag.py:418-430) for disp_est, disp_gt [B,H,W]; no gradient.  `meter`: the same launch
+    also adds the batch to that EpochMeter."""
     with torch.no_grad():
-        return StereoMetrics(_raw(disp_est.detach(), disp_gt, maxdisp))
+        return StereoMetrics(_raw(disp_est.detach(), disp_gt, maxdisp, meter))
 
 
 class MaskedSmoothL1Fn(torch.autograd.Function):
@@ -56,9 +90,9 @@ class MaskedSmoothL1Fn(torch.autograd.Function):
     backward in one kernel each, without the boolean gather (no stream synchronisation)."""
 
     @staticmethod
-    def forward(ctx, disp_est, disp_gt, maxdisp):
+    def forward(ctx, disp_est, disp_gt, maxdisp, meter=None):
         est = disp_est.contiguous()
-        out = _raw(est, disp_gt, maxdisp)
+        out = _raw(est, disp_gt, maxdisp, meter)
         ctx.save_for_backward(est, disp_gt.contiguous(), out)
         ctx.maxdisp = float(maxdisp)
         return out[0] * 1.0          # a kernel, not a memcpy (see ragmi_stereo_metrics_fwd on hipGraph memcpy nodes)
@@ -71,11 +105,13 @@ class MaskedSmoothL1Fn(torch.autograd.Function):
         d = torch.empty_like(est)
         check(load_library().ragmi_masked_smooth_l1_bwd(est.data_ptr(), gt.data_ptr(), out.data_ptr(), gout.data_ptr(), d.data_ptr(),
                                                         B, H, W, ctx.maxdisp, ops._stream()), "masked_smooth_l1_bwd")
-        return d, None, None
+        return d, None, None, None
 
 
-def masked_smooth_l1(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float = 192) -> torch.Tensor:
-    return MaskedSmoothL1Fn.apply(disp_est, disp_gt, maxdisp)
+def masked_smooth_l1(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float = 192, meter: Optional[EpochMeter] = None) -> torch.Tensor:
+    """`meter`: the loss launch is also the epoch meter's update for this batch (the reference scores the disp_est it trained on,
+    rag.py:386-396)."""
+    return MaskedSmoothL1Fn.apply(disp_est, disp_gt, maxdisp, meter)
 
 
 # --------------------------------------------------------------------------- self-supervised loss (src_self, supervise=False)

@@ -129,6 +129,11 @@ class _ConvBR(nn.Module):
             self._cache = (stamp, wk, scale, shift)
         return self._cache[1], self._cache[2], self._cache[3]
 
+    def forward_parameters(self) -> list:
+        """The parameters forward() reads: the weight, and the BatchNorm affine unless bn=False (that unit constructs a BatchNorm
+        it never calls)."""
+        return [self.conv.weight] + ([self.bn.weight, self.bn.bias] if self.use_bn else [])
+
     def autograd_mode(self, *inputs) -> bool:
         """Training composition needed: a gradient is wanted, or this unit's BatchNorm uses batch statistics."""
         return (ag.needs_grad(*inputs, self.conv.weight, self.bn.weight, self.bn.bias)
@@ -507,6 +512,18 @@ class _Cell(nn.Module):
             units = [m for m in self.modules() if isinstance(m, _ConvBR)]
             self.__dict__["_convbr_cache"] = units
         return units
+
+    def forward_parameters(self) -> list:
+        """The parameters forward() reads: preprocess, pre_preprocess unless prev_prev already has C_out channels (it is skipped
+        then, rag_model.py:150-151), and the conv branches of the genotype (every new state is concatenated into the output)."""
+        out = self.preprocess.forward_parameters()
+        if self.C_prev_prev != self.C_out:
+            out += self.pre_preprocess.forward_parameters()
+        for lst in self._contributions().values():
+            for _j, op in lst:
+                if isinstance(op, _ConvBR):
+                    out += op.forward_parameters()
+        return out
 
     def autograd_mode(self, *inputs) -> bool:
         units = self._convbrs()

@@ -156,6 +156,44 @@ class Network(MatchingNet):
         cost = self.search_matching(None, selected_ops, t, features=(lf, rf))
         return self.disp(cost)
 
+    # ------------------------------------------------------------------ the unit search's step (Appr.search_epoch, rag.py:344-406)
+    def search_mode(self):
+        """The module modes of search_epoch (rag.py:345-368): train() on the root, then eval() on every unit of the stems,
+        last_3_2d and the cells - reused and candidate alike, so the trunk's BatchNorms use and keep their running statistics
+        while the candidates' weights train; only the head lists stay in training mode.  Returns self."""
+        self.train()
+        for name in self._p_layers():
+            for unit in self._units(name):
+                unit.eval()
+        return self
+
+    def check_selected(self, t, selected_ops) -> List[int]:
+        """`selected_ops` as a list of ints after the checks of the unit-search step: one unit index per `p` layer, each inside
+        its ModuleList, and `t` inside the three head lists.  ValueError otherwise."""
+        names = self._p_layers()
+        if selected_ops is None or len(selected_ops) != len(names):
+            raise ValueError(f"selected_ops must name one unit for each of the {len(names)} layers of p (rag_model.py:403-498)")
+        sel = [int(v) for v in selected_ops]
+        for name, idx in zip(names, sel):
+            if not 0 <= idx < len(self._units(name)):
+                raise ValueError(f"selected_ops: unit {idx} of {name} does not exist ({len(self._units(name))} units)")
+        if t is None or isinstance(t, bool) or int(t) != t or not 0 <= int(t) < min(len(self.last_3_3d), len(self.last_6_3d), len(self.last_12_3d)):
+            raise ValueError(f"selected_ops: t = {t!r} is outside the head lists (last_3_3d / last_6_3d / last_12_3d)")
+        return sel
+
+    def active_parameters(self, t, selected_ops) -> list:
+        """The parameters a backward of search_forward(.., t, selected_ops) gives a gradient, read off the wiring: of every layer of
+        `p` the parameters unit selected_ops[k] reads in its forward, and of the head last_12_3d[t], last_6_3d[t] and
+        last_3_3d[t].conv.weight - those that require grad (after freeze_model / modify_param(new_models), rag.py:89-90, a reused
+        unit contributes nothing).  A bn=False unit constructs a BatchNorm it never calls: its affine is never included."""
+        sel = self.check_selected(t, selected_ops)
+        out = []
+        for name, idx in zip(self._p_layers(), sel):
+            out += self._units(name)[idx].forward_parameters()
+        for units in (self.last_12_3d, self.last_6_3d, self.last_3_3d):
+            out += units[int(t)].forward_parameters()
+        return [p for p in out if p.requires_grad]
+
     # ------------------------------------------------------------------ growth API
     def expand(self, t, genotype, device="cuda"):               # rag_model.py:391-522
         """Add one candidate unit per layer (built from `genotype`) and one head triple for task t; reset `p` so

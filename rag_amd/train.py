@@ -10,6 +10,12 @@ per-replica statistics, like the single-GPU reference per replica.
 The cell search's step (automl/mdenas_search.py:161-173 of both trees) is the same sequence on a supernet with one sampled
 operation per edge: `sampled_ops=(fea_ops, mat_ops)`.  Only the sampled operations receive gradients and torch.optim.SGD skips a
 parameter whose .grad is None, so that step updates `net.active_parameters(fea_ops, mat_ops)` alone (FlatSGD.set_active).
+
+The unit search's step (Appr.search_epoch / search_eval of approaches/rag.py:344-406, 443-470, run for every task t > 0) is the same
+sequence again on the expanded `Network` with one sampled unit per layer: `selected_ops=[unit per layer of p], t=<task>`.  The forward
+is `net.search_forward`, the update reaches `net.active_parameters(t, selected_ops)` alone, and `meter=` (rag_amd.metrics.EpochMeter)
+makes the loss launch the epoch meter's update.  The module modes are the caller's (`net.search_mode()`), and so are the sampling
+from `p`, h_e / h_a and the probability update.
 """
 from __future__ import annotations
 
@@ -64,12 +70,15 @@ class GradBucket:
         return total
 
 
-def masked_smooth_l1(disp: torch.Tensor, gt: torch.Tensor, maxdisp: int) -> torch.Tensor:
+def masked_smooth_l1(disp: torch.Tensor, gt: torch.Tensor, maxdisp: int, meter=None) -> torch.Tensor:
     """F.smooth_l1_loss(disp[mask], gt[mask]) with mask = 0 < gt < maxdisp (rag.py:210-211) without the boolean gather
-    (no stream synchronisation): the fused HIP loss of rag_amd.metrics on the GPU."""
+    (no stream synchronisation): the fused HIP loss of rag_amd.metrics on the GPU.  `meter` (rag_amd.metrics.EpochMeter, GPU only):
+    the same launch adds the batch's loss and metrics to it."""
     if disp.is_cuda:
         from .metrics import masked_smooth_l1 as fused
-        return fused(disp, gt, maxdisp)
+        return fused(disp, gt, maxdisp, meter)
+    if meter is not None:
+        raise RuntimeError("an EpochMeter is updated by the HIP loss launch: it needs the MI355X (there is no CPU meter)")
     mask = ((gt < maxdisp) & (gt > 0)).to(disp.dtype)          # host-side twin (CPU tests of the step logic)
     per = F.smooth_l1_loss(disp, gt, reduction="none")
     return (per * mask).sum() / mask.sum()
@@ -114,6 +123,33 @@ def _check_sampled(net, sampled_ops, gt, task_arch, features: bool, supervise: b
     return kind
 
 
+def _check_selected(net, selected_ops, t, gt, sampled_ops=None, task_arch=None, features: bool = False,
+                    supervise: bool = True) -> Optional[List[int]]:
+    """Argument checks of the unit-search step, before any launch.  -> selected_ops as a list of ints, or None without it."""
+    if selected_ops is None:
+        if t is not None:
+            raise ValueError("t is the head index of the unit search's step: it goes with selected_ops")
+        return None
+    if sampled_ops is not None or task_arch is not None or features or not supervise:
+        raise ValueError("selected_ops: the unit search runs search_forward on the images and trains supervised: sampled_ops, "
+                         "task_arch, features=True and supervise=False are refused")
+    if _is_depth(net):
+        raise ValueError("selected_ops: the depth network's unit search is not built; the step runs on the stereo rag_amd.Network")
+    from .network import Network
+    if not isinstance(net, Network):
+        raise ValueError("selected_ops is the unit search's step: net must be the stereo rag_amd.Network (after expand)")
+    if t is None:
+        raise ValueError("selected_ops: the step needs the task index t (the head it trains)")
+    if gt is None:
+        raise ValueError("selected_ops: the step needs the ground-truth disparity gt")
+    return net.check_selected(t, selected_ops)
+
+
+def _check_meter(meter, net, supervise: bool) -> None:
+    if meter is not None and (not supervise or _is_depth(net) or _supernet_kind(net) == "depth"):
+        raise ValueError("meter: an EpochMeter is fed by the masked smooth-L1 launch of the supervised stereo steps only")
+
+
 def _check_supervision(gt, features: bool, supervise: bool, depth: bool = False) -> None:
     if depth:
         if not supervise or features:
@@ -132,7 +168,8 @@ TRAIN_PRECISION = "fp32"     # the reference's training step is fp32 (rag.py:204
 
 
 def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None, features: bool = False,
-                     precision: Optional[str] = None, supervise: bool = True, sampled_ops: Optional[Sequence] = None):
+                     precision: Optional[str] = None, supervise: bool = True, sampled_ops: Optional[Sequence] = None,
+                     selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None):
     """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  A depth network (rag_amd.depth.Network):
     Network.forward_train(left) -> silog_loss(depth, gt) with gt the ground-truth depth in metres (0 = invalid) as in
     rag_depth/src/approaches/rag.py:232-242; `right` may be None.  `supervise=False`: the self-supervised loss
@@ -143,27 +180,36 @@ def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None
     class) or "f16x3" (opt-in; bound in include/rag_amd.h).  `sampled_ops=(fea_ops, mat_ops)`: `net` is a supernet
     (rag_amd.BasicNetwork / DepthBasicNetwork) and the step is the cell search's (automl/mdenas_search.py:161-173): forward
     net(left, right, fea_ops, mat_ops), masked smooth-L1 against net.maxdisp for the stereo supernet, silog_loss (gt > 0) for the
-    depth one; task_arch, features=True and supervise=False are refused, and so is a supernet without sampled_ops.  Returns the
+    depth one; task_arch, features=True and supervise=False are refused, and so is a supernet without sampled_ops.
+    `selected_ops=[unit per layer of p], t=<task>`: `net` is the expanded stereo Network and the step is the unit search's
+    (rag.py:371-382): forward net.search_forward(left, right, t, selected_ops), masked smooth-L1 against net.maxdisp; the module
+    modes are the caller's (net.search_mode()); sampled_ops, task_arch, features=True, supervise=False, another kind of net, a
+    missing t or gt, a wrong length and an index outside its list are refused.  `meter` (rag_amd.metrics.EpochMeter): the masked
+    smooth-L1 launch also adds this batch to the epoch's meter (rag.py:386-396 scores the disp_est it trained on).  Returns the
     (detached) loss."""
+    sel = _check_selected(net, selected_ops, t, gt, sampled_ops, task_arch, features, supervise)
     kind = _check_sampled(net, sampled_ops, gt, task_arch, features, supervise)
     depth = _is_depth(net)
-    if kind is None:
+    if kind is None and sel is None:
         _check_supervision(gt, features, supervise, depth)
+    _check_meter(meter, net, supervise)
     from . import ops
     with ops.conv_precision(precision or TRAIN_PRECISION):
-        if kind is not None:
+        if sel is not None:
+            loss = masked_smooth_l1(net.search_forward(left, right, int(t), sel), gt, net.maxdisp, meter)
+        elif kind is not None:
             out = net(left, right, sampled_ops[0], sampled_ops[1])
             if kind == "depth":
                 from .depth import silog_loss
                 loss = silog_loss(out, gt)
             else:
-                loss = masked_smooth_l1(out, gt, net.maxdisp)
+                loss = masked_smooth_l1(out, gt, net.maxdisp, meter)
         elif depth:
             from .depth import silog_loss
             loss = silog_loss(net.forward_train(left, 0, task_arch if task_arch is not None else net.arch_init), gt)
         else:
             disp = net(left, right, task_arch) if features else net(left, right, 0, task_arch if task_arch is not None else net.arch_init)
-            loss = masked_smooth_l1(disp, gt, net.maxdisp) if supervise else self_supervised_loss(disp, left, right)
+            loss = masked_smooth_l1(disp, gt, net.maxdisp, meter) if supervise else self_supervised_loss(disp, left, right)
         bucket.zero()
         loss.backward()
     return loss.detach()
@@ -274,15 +320,35 @@ def exchange_and_update(optimizer, bucket: GradBucket, *, clip: float = 5.0, dis
         p.grad = g
 
 
+def _active_of(net, sampled_ops, selected_ops, t) -> Optional[list]:
+    """The parameters the step updates: the sampled operations' / the sampled path's, or None (all of the bucket)."""
+    if selected_ops is not None:
+        return net.active_parameters(t, selected_ops)
+    return net.active_parameters(*sampled_ops) if sampled_ops is not None else None
+
+
+def search_eval_step(net, left, right, gt, t, selected_ops, meter=None):
+    """One batch of Appr.search_eval (rag.py:448-466): stereo_metrics(net.search_forward(left, right, t, selected_ops), gt,
+    net.maxdisp) under no_grad, with `net` in eval() (the caller's, as in rag.py:445; a net in training mode is refused); `meter`
+    (rag_amd.metrics.EpochMeter) takes the batch in the same launch.  The argument checks of the training step's selected_ops."""
+    sel = _check_selected(net, selected_ops, t, gt)
+    if net.training:
+        raise ValueError("search_eval_step: net must be in eval() (Appr.search_eval, rag.py:445)")
+    from .metrics import stereo_metrics
+    with torch.no_grad():
+        return stereo_metrics(net.search_forward(left, right, int(t), sel), gt, net.maxdisp, meter=meter)
+
+
 def train_step(net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                features: bool = False, precision: Optional[str] = None, supervise: bool = True,
-               sampled_ops: Optional[Sequence] = None):
-    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision`, `supervise` and `sampled_ops` as in
-    forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops` the optimizer updates
-    net.active_parameters(*sampled_ops) only (exchange_and_update).  Returns the (detached) loss."""
+               sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None):
+    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision`, `supervise`, `sampled_ops`, `selected_ops` / `t`
+    and `meter` as in forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops` the optimizer updates
+    net.active_parameters(*sampled_ops) only (exchange_and_update), with `selected_ops` (one batch of Appr.search_epoch,
+    rag.py:371-396) net.active_parameters(t, selected_ops).  Returns the (detached) loss."""
     loss = forward_backward(net, bucket, left, right, gt, task_arch=task_arch, features=features, precision=precision,
-                            supervise=supervise, sampled_ops=sampled_ops)
-    active = net.active_parameters(*sampled_ops) if sampled_ops is not None else None
+                            supervise=supervise, sampled_ops=sampled_ops, selected_ops=selected_ops, t=t, meter=meter)
+    active = _active_of(net, sampled_ops, selected_ops, t)
     exchange_and_update(optimizer, bucket, clip=clip, dist=dist, active=active)
     return loss
 
@@ -318,20 +384,27 @@ class GraphedTrainStep:
     `sampled_ops=(fea_ops, mat_ops)`: the cell search's step on a supernet (forward_backward).  The search keeps its ops for an
     epoch, so it builds one object per epoch over the same bucket and optimizer (momentum carries over); the warm-up steps are real
     steps on the given batch, so with warmup=1 the constructor IS the epoch's first step, `first_loss` is its loss, and later calls
-    replay.  Batch size 1 stays refused by the census as for the grown network (torch.cat of 5-D tensors is a copy there)."""
+    replay.  Batch size 1 stays refused by the census as for the grown network (torch.cat of 5-D tensors is a copy there).
+
+    `selected_ops=, t=, meter=`: the unit search's step (forward_backward), one object per epoch in the same way (a path holds for an
+    epoch, rag.py:275-290).  The meter's update is part of the captured loss launch: every replay adds its batch to `meter.sums`, and
+    `meter.last` stays the static vector the replays rewrite."""
 
     def __init__(self, net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                  features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True,
-                 sampled_ops: Optional[Sequence] = None):
-        if _check_sampled(net, sampled_ops, gt, task_arch, features, supervise) is None:
+                 sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None):
+        sel = _check_selected(net, selected_ops, t, gt, sampled_ops, task_arch, features, supervise)
+        if _check_sampled(net, sampled_ops, gt, task_arch, features, supervise) is None and sel is None:
             _check_supervision(gt, features, supervise, _is_depth(net))
-        self._active = net.active_parameters(*sampled_ops) if sampled_ops is not None else None
+        _check_meter(meter, net, supervise)
+        self._active = _active_of(net, sampled_ops, sel, t)
         self.net, self.opt, self.bucket, self.clip, self.dist = net, optimizer, bucket, clip, dist
         self.left = left.clone()
         self.right = right.clone() if right is not None else None
         self.gt = gt.clone() if gt is not None else None
         self.precision = precision or TRAIN_PRECISION
-        kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise, sampled_ops=sampled_ops)
+        kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise, sampled_ops=sampled_ops,
+                  selected_ops=sel, t=t, meter=meter)
         self.first_loss = None                         # loss of the first warm-up step (a real step on the given batch)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
