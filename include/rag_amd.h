@@ -610,6 +610,16 @@ int ragmi_depth_head_fwd(const void* y, const void* w3, const void* w1, const vo
 int ragmi_depth_metrics_workspace_elems(long long n);
 int ragmi_depth_metrics_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10, int dtype,
                             void* stream);
+/* The same two launches on the same kernels, for one batch of the unit search's loops (approaches/rag.py:401-427, 501-522).  Either
+ * of the two further pointers may be null; both must be 8-byte aligned.
+ *   saved3  (double[3]): {n, mean d, sqrt(mean d^2 - variance_focus mean(d)^2)}, what ragmi_silog_loss_fwd saves: with it
+ *           ragmi_silog_loss_bwd is the backward of out10[0] (bit for bit the loss of ragmi_silog_loss_fwd).
+ *   meter12 (double[12]): the epoch's meter.  The finalize kernel's one thread stores out10, then meter[k] += (double)out10[k] for
+ *           k = 0..9 (the float it just stored), meter[10] += 1 (batches), meter[11] += n (masked pixels).  No atomics, no memset,
+ *           no extra launch; a batch with no masked pixel adds NaN (the reference's numpy mean of an empty selection).
+ * The caller zeroes meter12 at the start of an epoch. */
+int ragmi_depth_metrics_meter_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10,
+                                  void* saved3, void* meter12, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Backward of ragmi_depth_head_fwd (the depth training step, rag_depth/src/approaches/rag.py:182-246; the forward chain is

@@ -26,12 +26,16 @@ from . import supernet  # noqa: E402,F401
 from .supernet import AutoFeature, AutoMatching, BasicNetwork, DepthAutoMatching, DepthBasicNetwork  # noqa: E402,F401
 from . import depth  # noqa: E402,F401
 depth.BasicNetwork = DepthBasicNetwork      # the depth tree's own name for its supernet (rag_depth/src/automl/mdenas_basicmodel.py)
-from .depth import DepthNetwork, load_depth_checkpoint  # noqa: E402,F401
+from .depth import DepthEpochMeter, DepthNetwork, depth_metrics, load_depth_checkpoint, silog_metrics_loss  # noqa: E402,F401
+from . import depth_search  # noqa: E402,F401
+from .depth_search import DepthGraphedSearchStep, depth_search_eval_step, depth_search_step  # noqa: E402,F401
 from . import data  # noqa: E402,F401
 from .data import color_stats, lanczos_taps, prepare_batch, random_crop_origin, resize_lanczos, resize_lanczos_torch, transfer_color  # noqa: E402,F401
 
 __all__ = [
     "EpochMeter", "search_eval_step",
+    "DepthEpochMeter", "depth_metrics", "silog_metrics_loss", "depth_search", "depth_search_step", "depth_search_eval_step",
+    "DepthGraphedSearchStep",
     "Network", "Cell_2d", "ConvBR_2d", "DepthNetwork", "load_depth_checkpoint",
     "data", "prepare_batch", "random_crop_origin", "color_stats", "transfer_color", "lanczos_taps", "resize_lanczos", "resize_lanczos_torch",
     "ops", "load_library", "lib_path", "MatchingNet", "Cell_3d", "ConvBR_3d", "Identity_3d", "Disp",

@@ -145,6 +145,8 @@ SIGNATURES = {
                                      c_float, c_int, c_void_p]),
     "ragmi_depth_metrics_workspace_elems": (c_int, [ctypes.c_longlong]),
     "ragmi_depth_metrics_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "ragmi_depth_metrics_meter_fwd": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_void_p]),
     "ragmi_depth_head_bwd_workspace_elems": (c_int64, [c_int, c_int, c_int, c_int]),
     "ragmi_depth_head_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),

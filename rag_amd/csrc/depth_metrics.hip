@@ -54,8 +54,14 @@ __global__ __launch_bounds__(DM_WG) void depth_metrics_kernel(const float* __res
 }
 
 // out = silog_loss, then compute_errors: silog, abs_rel, log10, rms, sq_rel, log_rms, d1, d2, d3
+// saved (may be null): {n, mean d, sqrt(md2 - vf md^2)}, what silog_finalize_kernel (depth_train.hip) saves for silog_bwd_kernel, so
+// out[0] is a training loss with ragmi_silog_loss_bwd as its backward.
+// meter (may be null): the epoch's meter of search_epoch / search_eval (approaches/rag.py:401-427, 501-522) as 12 doubles, updated by
+// this one thread after it stored `out`: meter[0..9] += the ten floats just stored (the reference adds per-batch floats; a batch with
+// no valid pixel adds NaN, as numpy's mean of an empty selection does there), meter[10] += 1 (batches), meter[11] += n.
 __global__ __launch_bounds__(DM_WG) void depth_metrics_finalize_kernel(const double* __restrict__ slots, int nslots, double variance_focus,
-                                                                       float* __restrict__ out) {
+                                                                       float* __restrict__ out, double* __restrict__ saved,
+                                                                       double* __restrict__ meter) {
   double v[DM_NSUM];
 #pragma unroll
   for (int k = 0; k < DM_NSUM; ++k) v[k] = 0.0;
@@ -78,7 +84,8 @@ __global__ __launch_bounds__(DM_WG) void depth_metrics_finalize_kernel(const dou
   if (threadIdx.x == 0) {
     const double n = red[0][0];                       // 0 masked pixels: every mean is 0/0 = NaN, as numpy's mean of an empty array
     const double md = red[1][0] / n, md2 = red[2][0] / n;
-    out[0] = (float)(sqrt(md2 - variance_focus * md * md) * 10.0);
+    const double sa = sqrt(md2 - variance_focus * md * md);
+    out[0] = (float)(sa * 10.0);
     out[1] = (float)(sqrt(md2 - md * md) * 100.0);
     out[2] = (float)(red[3][0] / n);
     out[3] = (float)(red[6][0] / n);
@@ -88,10 +95,32 @@ __global__ __launch_bounds__(DM_WG) void depth_metrics_finalize_kernel(const dou
     out[7] = (float)(red[7][0] / n);
     out[8] = (float)(red[8][0] / n);
     out[9] = (float)(red[9][0] / n);
+    if (saved) {
+      saved[0] = n;
+      saved[1] = md;
+      saved[2] = sa;
+    }
+    if (meter) {
+      for (int k = 0; k < DM_NSUM; ++k) meter[k] += (double)out[k];
+      meter[10] += 1.0;
+      meter[11] += n;
+    }
   }
 }
 
 static int depth_metrics_slots(long long n) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 4 * DM_WG), DM_MAXWG)); }
+
+// the two launches of both entry points; `saved` / `meter` null: the finalize kernel stores `out` only
+static int depth_metrics_launch(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10,
+                                void* saved3, void* meter12, void* stream) {
+  const int nslots = depth_metrics_slots(n);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(depth_metrics_kernel, dim3((unsigned)nslots), dim3(DM_WG), 0, st, (const float*)est, (const float*)gt, (int64_t)n,
+                     (double*)workspace);
+  hipLaunchKernelGGL(depth_metrics_finalize_kernel, dim3(1), dim3(DM_WG), 0, st, (const double*)workspace, nslots, (double)variance_focus,
+                     (float*)out10, (double*)saved3, (double*)meter12);
+  return check_launch("depth_metrics");
+}
 
 }  // namespace ragmi
 
@@ -107,11 +136,17 @@ extern "C" int ragmi_depth_metrics_fwd(const void* est, const void* gt, long lon
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "depth_metrics: dtype %d not built (float32 only)", dtype);
   RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "depth_metrics: bad size %lld", n);
   RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "depth_metrics: workspace not 8-byte aligned");
-  const int nslots = depth_metrics_slots(n);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(depth_metrics_kernel, dim3((unsigned)nslots), dim3(DM_WG), 0, st, (const float*)est, (const float*)gt, (int64_t)n,
-                     (double*)workspace);
-  hipLaunchKernelGGL(depth_metrics_finalize_kernel, dim3(1), dim3(DM_WG), 0, st, (const double*)workspace, nslots, (double)variance_focus,
-                     (float*)out10);
-  return check_launch("depth_metrics");
+  return depth_metrics_launch(est, gt, n, variance_focus, workspace, out10, nullptr, nullptr, stream);
+}
+
+extern "C" int ragmi_depth_metrics_meter_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace,
+                                             void* out10, void* saved3, void* meter12, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(est && gt && workspace && out10, RAGMI_EINVAL, "depth_metrics_meter: null pointer");
+  RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "depth_metrics_meter: dtype %d not built (float32 only)", dtype);
+  RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "depth_metrics_meter: bad size %lld", n);
+  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "depth_metrics_meter: workspace not 8-byte aligned");
+  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(saved3) & 7) == 0 && (reinterpret_cast<uintptr_t>(meter12) & 7) == 0, RAGMI_EINVAL,
+                "depth_metrics_meter: saved3 / meter12 not 8-byte aligned");
+  return depth_metrics_launch(est, gt, n, variance_focus, workspace, out10, saved3, meter12, stream);
 }

@@ -17,6 +17,10 @@ the `rag_amd.autograd` Functions (train-mode BatchNorm where a unit is in train(
 forward launch; its backward is ``ops.depth_head_bwd``).  `silog_loss` is the loss of that step (utilstool/experiment.py:154-161)
 with its fused HIP gradient; ``rag_amd.train`` drives both.  `search_forward` and a standalone `DispHead` stay inference only.
 
+``search_forward_train(left, t, selected_ops)`` is the training forward of Appr.search_epoch (approaches/rag.py:371-427): one unit per
+layer of `p` and the heads of task t.  `silog_metrics_loss` is that loop's loss, error metrics and epoch meter (`DepthEpochMeter`) as
+the ONE pass of `depth_metrics`; ``rag_amd.depth_search`` drives the step.
+
 `load_depth_checkpoint` rebuilds a grown model from the reference's ``checkpoint_task{t}.ckpt`` (``train()`` it to fine-tune or grow
 a task); `depth_metrics` is the eval loop's silog_loss + compute_errors (approaches/rag.py:440-489) in one fused pass.
 """
@@ -131,6 +135,77 @@ def silog_loss_torch(est: torch.Tensor, gt: torch.Tensor, variance_focus: float 
     return torch.sqrt((d ** 2).mean() - variance_focus * (d.mean() ** 2)) * 10.0
 
 
+class DepthEpochMeter:
+    """The epoch's running sums of Appr.search_epoch / search_eval / eval (approaches/rag.py:397-436, 441-490, 493-529) on the device.
+    The reference copies the full depth_est and depth_gt maps to the host after every batch, gathers the masked pixels in numpy, runs
+    compute_errors there and adds one `.item()` for the loss; here the finalize kernel of the loss / metrics launch adds the batch's ten
+    floats to `sums` (ragmi_depth_metrics_meter_fwd: no extra launch, nothing leaves the device) and `mean()` is the epoch's one
+    device-to-host copy.
+
+    `sums`: float64 [12] - running sums of the ten DEPTH_NAMES (each batch's float added in double), the number of batches, the
+    masked pixels.  The reference accumulates abs_rel and rmse in numpy float32 (compute_errors returns float32 for its entries 0-5
+    and `0 + np.float32` stays float32) and d1-d3 and the loss in double; the meter accumulates all ten in double, so its means
+    differ from the reference's float32 ones by at most (batches) x 2^-24 relative.  A batch without a valid pixel adds NaN, as
+    numpy's mean of an empty selection does there.  `last`: the most recent batch's 10-float vector (the kernel's `out` itself,
+    not a copy; None before the first batch)."""
+
+    def __init__(self, device):
+        self.sums = torch.zeros((12,), device=device, dtype=torch.float64)
+        self.last = None
+
+    def reset(self) -> None:
+        self.sums.zero_()
+        self.last = None
+
+    def mean(self) -> Dict[str, float]:
+        """DEPTH_NAMES -> sums[k] / sums[10] as Python floats (nan before the first batch)."""
+        vals = self.sums.tolist()          # the only synchronisation
+        n = vals[10]
+        return {k: (v / n if n else float("nan")) for k, v in zip(DEPTH_NAMES, vals[:10])}
+
+
+METER_NEEDS_GPU = "a DepthEpochMeter is updated by the HIP metrics launch: it needs the MI355X (there is no CPU meter)"
+
+
+def _check_meter(meter, device) -> None:
+    if meter is not None and (not isinstance(meter, DepthEpochMeter) or meter.sums.device != device):
+        raise ValueError("meter must be a rag_amd.depth.DepthEpochMeter on the device of the depth maps")
+
+
+class SilogMetricsLossFn(torch.autograd.Function):
+    """silog_loss as out[0] of the depth-metrics pass (two launches: the loss, the nine compute_errors entries, the saved scalars of
+    the backward and, with a meter, its update); the backward is ops.silog_loss_bwd (one launch)."""
+
+    @staticmethod
+    def forward(ctx, est, gt, variance_focus, meter):
+        saved = torch.empty((3,), device=est.device, dtype=torch.float64)
+        out = ops.depth_metrics(est.detach(), gt.detach(), variance_focus, saved=saved, meter=meter.sums if meter is not None else None)
+        if meter is not None:
+            meter.last = out
+        ctx.vf = float(variance_focus)
+        ctx.save_for_backward(est, gt, saved)
+        return out[0] * 1.0          # a kernel, not a memcpy node (as MaskedSmoothL1Fn)
+
+    @staticmethod
+    def backward(ctx, grad):
+        est, gt, saved = ctx.saved_tensors
+        return ops.silog_loss_bwd(est.detach(), gt, saved, grad, ctx.vf), None, None, None
+
+
+def silog_metrics_loss(est: torch.Tensor, gt: torch.Tensor, meter: Optional[DepthEpochMeter] = None,
+                       variance_focus: float = 0.85) -> torch.Tensor:
+    """`silog_loss` of one batch of the unit search (approaches/rag.py:407-427) as a 0-d tensor with a gradient w.r.t. `est`, computed
+    by the depth-metrics pass: the same two launches also give compute_errors' nine entries of the batch (`meter.last`) and add all
+    ten to `meter` (DepthEpochMeter), where the reference copies both maps to the host.  Bit for bit the loss and the gradient of
+    `silog_loss`.  On the CPU `silog_loss_torch`; a meter there raises (there is no CPU meter)."""
+    if est.is_cuda:
+        _check_meter(meter, est.device)
+        return SilogMetricsLossFn.apply(est, gt, float(variance_focus), meter)
+    if meter is not None:
+        raise RuntimeError(METER_NEEDS_GPU)
+    return silog_loss_torch(est, gt, variance_focus)
+
+
 class Network(_StereoNetwork):
     """rag_depth/src/models/rag_model.py:201-800.  Same constructor, attributes, ModuleList names and state_dict keys as the
     reference; `depth_head` (never grown) and `max_depth = 80` in place of the stereo head."""
@@ -190,12 +265,17 @@ class Network(_StereoNetwork):
         """stem3d0 -> stem3d1 -> cells (rag_model.py:363-373), then the head's 1x1 part: the input of upsample_6, at (h/2, w/2) or
         already at (h, w) (rag_model.py:378-385).  `train`: the unfused m6(m12(.), resample_to=half) chain, whose units have
         autograd forms (the one-launch 1x1 chain is inference only)."""
+        return self._trunk_head(self._trunk_cells(x, stem0, stem1, cells), x.shape[2], x.shape[3], m6, m12, train)
+
+    @staticmethod
+    def _trunk_cells(x, stem0, stem1, cells) -> torch.Tensor:
         out = (stem0(x),)
         out = (out[0], stem1(out[0]))
         for c in cells:
             out = c(out[0], out[1])
-        last = out[-1]
-        h, w = x.shape[2], x.shape[3]
+        return out[-1]
+
+    def _trunk_head(self, last, h: int, w: int, m6, m12, train: bool = False) -> torch.Tensor:
         if last.shape[2] == h:
             return last
         if last.shape[2] == h // 2:
@@ -277,6 +357,34 @@ class Network(_StereoNetwork):
         cells = [cell[selected_ops[i + 10]] for i, cell in enumerate(self.cells_3d)]
         y6 = self._trunk(x, self.stem3d0[selected_ops[8]], self.stem3d1[selected_ops[9]], cells, self.last_6_3d[t], self.last_12_3d[t])
         return self._head(y6, x.shape[2:], self.last_3_3d[t])
+
+    def search_forward_train(self, left, t, selected_ops):         # rag_model.py:716-740 under autograd (approaches/rag.py:405)
+        """The training forward of a sampled path: `search_forward` on the composition of `forward_train`, -> depth [B, 3h, 3w] with
+        an autograd graph.  The module modes are the caller's (`search_mode()`: the trunk's BatchNorms on running statistics, the
+        heads of task t on batch statistics).  When no selected trunk unit has a parameter that requires grad (a path that reuses
+        every unit) the trunk runs without a graph, on the inference forms up to the last cell's output, and only the head's tensors
+        train.  fp32 only."""
+        if self.act_dtype != torch.float32 or left.dtype != torch.float32:
+            raise RuntimeError("rag_amd.depth.Network: training is fp32 only")
+        sel = self.check_selected(t, selected_ops)
+        trunk = [self._units(name)[idx] for name, idx in zip(self._p_layers(), sel)]
+        graph = torch.is_grad_enabled() and (left.requires_grad or any(p.requires_grad for u in trunk for p in u.forward_parameters()))
+        with torch.set_grad_enabled(graph):
+            x = self.search_feature(left, sel)
+            last = self._trunk_cells(x, trunk[8], trunk[9], trunk[10:])
+        m3, m6, m12 = self.last_3_3d[int(t)], self.last_6_3d[int(t)], self.last_12_3d[int(t)]
+        y6 = self._trunk_head(last, x.shape[2], x.shape[3], m6, m12, train=True)
+        if m3.use_bn or m3.relu or m3._geometry() != 3 or m3.conv.out_channels != 1:
+            raise NotImplementedError("rag_amd.depth.Network: last_3_3d must be the reference's 3x3 conv without BN / ReLU")
+        dh = self.depth_head.conv1
+        return DepthHeadFn.apply(y6, m3.conv.weight, dh.weight, dh.bias, x.shape[2:], 3, float(self.max_depth))
+
+    def active_parameters(self, t, selected_ops) -> list:
+        """The stereo network's set (the selected units and the heads of task t, those that require grad), and the depth head's
+        conv1 weight and bias when they require grad (after freeze_model + modify_param(new_models) they do not: `depth_head` is in
+        no model list, rag_model.py:553-638)."""
+        dh = self.depth_head.conv1
+        return super().active_parameters(t, selected_ops) + [p for p in (dh.weight, dh.bias) if p.requires_grad]
 
 
 DepthNetwork = Network
@@ -375,11 +483,19 @@ class DepthMetrics:
         return dict(zip(DEPTH_NAMES, self.tensor.tolist()))      # the only synchronisation
 
 
-def depth_metrics(depth_est: torch.Tensor, depth_gt: torch.Tensor, variance_focus: float = 0.85) -> DepthMetrics:
+def depth_metrics(depth_est: torch.Tensor, depth_gt: torch.Tensor, variance_focus: float = 0.85,
+                  meter: Optional[DepthEpochMeter] = None) -> DepthMetrics:
     """silog_loss + compute_errors of the depth eval loop (approaches/rag.py:440-489) over the pixels with gt > 0 of the whole batch,
-    on the device, without the boolean gather or the per-batch D2H copy; no gradient."""
+    on the device, without the boolean gather or the per-batch D2H copy; no gradient.  `meter` (DepthEpochMeter): the same launch
+    also adds the batch to it."""
+    if isinstance(meter, DepthEpochMeter) and not depth_est.is_cuda:
+        raise RuntimeError(METER_NEEDS_GPU)
+    _check_meter(meter, depth_est.device)
     with torch.no_grad():
-        return DepthMetrics(ops.depth_metrics(depth_est.detach(), depth_gt.detach(), variance_focus))
+        out = ops.depth_metrics(depth_est.detach(), depth_gt.detach(), variance_focus, meter=meter.sums if meter is not None else None)
+    if meter is not None:
+        meter.last = out
+    return DepthMetrics(out)
 
 
 # ---------------------------------------------------------------------------------------------------------------- plain-torch twins

@@ -1103,9 +1103,12 @@ def depth_head(y: torch.Tensor, w3: torch.Tensor, w1: torch.Tensor, b1: torch.Te
     return out
 
 
-def depth_metrics(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85) -> torch.Tensor:
+def depth_metrics(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0.85, saved: Optional[torch.Tensor] = None,
+                  meter: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[silog_loss, silog, abs_rel, log10, rms, sq_rel, log_rms, d1, d2, d3] over the pixels with gt > 0 of the whole batch, as a
-    10-float device tensor (two launches, no sync)."""
+    10-float device tensor (two launches, no sync).  `saved` (float64 [3]): also receives the input of `silog_loss_bwd`, which is
+    then the backward of out[0].  `meter` (float64 [12]): the same launch adds the ten floats, one batch and the masked pixel count
+    to it (ragmi_depth_metrics_meter_fwd)."""
     for t in (est, gt):
         if not t.is_cuda:
             raise RuntimeError("rag_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
@@ -1117,6 +1120,14 @@ def depth_metrics(est: torch.Tensor, gt: torch.Tensor, variance_focus: float = 0
     n = est.numel()
     ws = torch.empty((max(2, lib.ragmi_depth_metrics_workspace_elems(n)),), device=est.device, dtype=torch.float32)
     out = torch.empty((10,), device=est.device, dtype=torch.float32)
+    if saved is not None or meter is not None:
+        for t, k in ((saved, 3), (meter, 12)):
+            if t is not None and (t.dtype != torch.float64 or t.device != est.device or t.numel() != k or not t.is_contiguous()):
+                raise ValueError(f"depth_metrics: saved / meter must be contiguous float64 [{k}] on the device of est")
+        check(lib.ragmi_depth_metrics_meter_fwd(est.data_ptr(), gt.data_ptr(), n, float(variance_focus), ws.data_ptr(), out.data_ptr(),
+                                                saved.data_ptr() if saved is not None else None,
+                                                meter.data_ptr() if meter is not None else None, dt, _stream()), "depth_metrics_meter")
+        return out
     check(lib.ragmi_depth_metrics_fwd(est.data_ptr(), gt.data_ptr(), n, float(variance_focus), ws.data_ptr(), out.data_ptr(), dt,
                                       _stream()), "depth_metrics")
     return out

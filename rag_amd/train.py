@@ -134,7 +134,8 @@ def _check_selected(net, selected_ops, t, gt, sampled_ops=None, task_arch=None, 
         raise ValueError("selected_ops: the unit search runs search_forward on the images and trains supervised: sampled_ops, "
                          "task_arch, features=True and supervise=False are refused")
     if _is_depth(net):
-        raise ValueError("selected_ops: the depth network's unit search is not built; the step runs on the stereo rag_amd.Network")
+        raise ValueError("selected_ops: the depth network's unit search is not built into this entry point: use "
+                         "rag_amd.depth_search_step / depth_search_eval_step / DepthGraphedSearchStep")
     from .network import Network
     if not isinstance(net, Network):
         raise ValueError("selected_ops is the unit search's step: net must be the stereo rag_amd.Network (after expand)")
@@ -364,7 +365,55 @@ def graph_census(graph: "torch.cuda.CUDAGraph") -> dict:
     return dict(zip(("kernel", "memcpy", "memset", "other"), (v.value for v in n)))
 
 
-class GraphedTrainStep:
+class _GraphedStep:
+    """What GraphedTrainStep and rag_amd.depth_search.DepthGraphedSearchStep share: warm-up steps on a side stream, the capture of
+    forward + loss + backward, the node census that refuses memcpy / memset nodes, and the replay followed by the eager update.  A
+    subclass sets net, opt, bucket, clip, dist and _active, then calls `_capture(run, warmup)` with `run()` = its forward_backward
+    on its static input buffers."""
+
+    def _capture(self, run, warmup: int) -> None:
+        net, name = self.net, type(self).__name__
+        self.first_loss = None                         # loss of the first warm-up step (a real step on the given batch)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                  # warm-up on a side stream: lazy state (allocator pools, occupancy
+            for _ in range(max(warmup, 1)):            # queries, momentum buffers) exists before capture
+                loss = run()
+                exchange_and_update(self.opt, self.bucket, clip=self.clip, dist=self.dist, active=self._active)
+                if self.first_loss is None:
+                    self.first_loss = loss
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph(keep_graph=True)     # keep the hipGraph_t: its nodes are inspected below
+        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):   # RCCL's watchdog thread must not trip it
+            self.loss = run()
+        self.node_census = self._census()
+        if self.node_census["memcpy"] or self.node_census["memset"]:
+            raise RuntimeError(
+                f"{name}: the captured step holds {self.node_census['memcpy']} memcpy and {self.node_census['memset']} "
+                "memset node(s); such nodes are not replay-safe on this runtime (DESIGN.md 4.4).  tools/find_memcpy_ops.py lists "
+                "the ATen calls behind them; run the step eagerly (rag_amd.train.train_step) until they are kernels.")
+        self.graph.instantiate()
+        # train-mode BatchNorm buffers change at every replay through raw pointers: their version counters are bumped by hand
+        # (the eval-mode caches of rag_amd.modules key on them)
+        self._bn_buffers = [t for m in net.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training
+                            and m.track_running_stats for t in (m.running_mean, m.running_var, m.num_batches_tracked) if t is not None]
+
+    def _census(self) -> dict:
+        return graph_census(self.graph)
+
+    def _replay(self, pairs):
+        """Copy the new inputs `(static buffer, tensor or None)` in, replay the graph, update eagerly.  -> the static loss."""
+        for dst, src in pairs:
+            if src is not None and dst is not None and src.data_ptr() != dst.data_ptr():
+                dst.copy_(src)
+        self.graph.replay()
+        if self._bn_buffers:
+            torch.autograd.graph.increment_version(self._bn_buffers)
+        exchange_and_update(self.opt, self.bucket, clip=self.clip, dist=self.dist, active=self._active)
+        return self.loss
+
+
+class GraphedTrainStep(_GraphedStep):
     """The same step with forward + loss + backward replayed as ONE captured hipGraph (the ~2500 kernel launches of a
     step cost more host time than GPU time when issued one by one); the gradient exchange, clipping and the optimizer
     step stay eager (a handful of launches, and the collective stays outside the graph).  Inputs are copied into static
@@ -405,43 +454,10 @@ class GraphedTrainStep:
         self.precision = precision or TRAIN_PRECISION
         kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise, sampled_ops=sampled_ops,
                   selected_ops=sel, t=t, meter=meter)
-        self.first_loss = None                         # loss of the first warm-up step (a real step on the given batch)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                  # warm-up on a side stream: lazy state (allocator pools, occupancy
-            for _ in range(max(warmup, 1)):            # queries, momentum buffers) exists before capture
-                loss = forward_backward(net, bucket, self.left, self.right, self.gt, **kw)
-                exchange_and_update(optimizer, bucket, clip=clip, dist=dist, active=self._active)
-                if self.first_loss is None:
-                    self.first_loss = loss
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph(keep_graph=True)     # keep the hipGraph_t: its nodes are inspected below
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):   # RCCL's watchdog thread must not trip it
-            self.loss = forward_backward(net, bucket, self.left, self.right, self.gt, **kw)
-        self.node_census = self._census()
-        if self.node_census["memcpy"] or self.node_census["memset"]:
-            raise RuntimeError(
-                f"GraphedTrainStep: the captured step holds {self.node_census['memcpy']} memcpy and {self.node_census['memset']} "
-                "memset node(s); such nodes are not replay-safe on this runtime (DESIGN.md 4.4).  tools/find_memcpy_ops.py lists "
-                "the ATen calls behind them; run the step eagerly (rag_amd.train.train_step) until they are kernels.")
-        self.graph.instantiate()
-        # train-mode BatchNorm buffers change at every replay through raw pointers: their version counters are bumped by hand
-        # (the eval-mode caches of rag_amd.modules key on them)
-        self._bn_buffers = [t for m in net.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training
-                            and m.track_running_stats for t in (m.running_mean, m.running_var, m.num_batches_tracked) if t is not None]
-
-    def _census(self) -> dict:
-        return graph_census(self.graph)
+        self._capture(lambda: forward_backward(net, bucket, self.left, self.right, self.gt, **kw), warmup)
 
     def __call__(self, left=None, right=None, gt=None):
-        for dst, src in ((self.left, left), (self.right, right), (self.gt, gt)):
-            if src is not None and dst is not None and src.data_ptr() != dst.data_ptr():
-                dst.copy_(src)
-        self.graph.replay()
-        if self._bn_buffers:
-            torch.autograd.graph.increment_version(self._bn_buffers)
-        exchange_and_update(self.opt, self.bucket, clip=self.clip, dist=self.dist, active=self._active)
-        return self.loss
+        return self._replay(((self.left, left), (self.right, right), (self.gt, gt)))
 
 
 def make_optimizer(params, lr: float = 1e-3, momentum: float = 0.9, weight_decay: float = 3e-3, bucket: Optional[GradBucket] = None):
