@@ -404,6 +404,30 @@ int ragmi_disp_softargmin_fwd(const void* cost, void* out, int B, int d, int h, 
 int ragmi_disparity_regression_fwd(const void* prob, void* out, int B, int D, int H, int W,
                                    int dtype, void* stream);
 
+/*
+ * The head with per-pixel statistics of its distribution, in the same pass (rag_model.py:18-44 computes the
+ * distribution and keeps only its mean).  p_k, k = 0 .. maxdisp-1, is the Softmin over the trilinearly upsampled
+ * cost (align_corners=False, to [maxdisp, Ho, Wo]) exactly as in ragmi_disp_softargmin_fwd.  Per output pixel:
+ *   out      = sum_k p_k k                     the SAME BITS as ragmi_disp_softargmin_fwd on the same input
+ *   variance = sum_k p_k (k - out)^2           px^2, accumulated about a pivot near the mode (not sum p k^2 - out^2)
+ *   peak     = max_k p_k
+ *   entropy  = -sum_k p_k ln p_k               nats; a term with p_k = 0 contributes 0
+ * out: [B, Ho, Wo] fp32.  stats: [B, 3, Ho, Wo] fp32, planes (variance, peak, entropy).  cost: fp32 or bf16 storage.
+ * One launch; arguments, refusals, status codes and the choice between the tiled and the generic kernel are those of
+ * ragmi_disp_softargmin_fwd.  No allocation, synchronisation, memset, memcpy or atomics; bitwise reproducible.
+ * Non-finite costs give unspecified statistics, never an access out of bounds.
+ */
+int ragmi_disp_softargmin_stats_fwd(const void* cost, void* out, void* stats, int B, int d, int h, int w,
+                                    int maxdisp, int Ho, int Wo, int dtype, void* stream);
+
+/*
+ * DisparityRegression.forward (rag_model.py:18-29) with the same statistics of prob[B, D, H, W], taken as given (not
+ * renormalised): out = the bits of ragmi_disparity_regression_fwd; stats [B, 3, H, W] by the definitions above with
+ * p = prob, terms of p <= 0 contributing 0 to the entropy.  A one-hot prob has variance 0, peak 1, entropy 0 exactly.
+ */
+int ragmi_disparity_regression_stats_fwd(const void* prob, void* out, void* stats, int B, int D, int H, int W,
+                                         int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Cost volume + stem3d0 in one step, without materialising the cost volume (rag_model.py:375-383 followed by
  * ConvBR_3d(2C, Cout, 3, 1, 1), rag_model.py:234/341).  The left half of the cost volume does not depend on the disparity

@@ -148,3 +148,9 @@ class MultiTaskStereo(nn.Module):
         if not 0 <= t < len(self.archis):
             raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
         return self.net(left, right, t, self.archis[t])
+
+    def forward_stats(self, left, right, t: int, out=None, stats=None):
+        """forward with the disparity distribution's per-pixel statistics (Network.forward_stats) -> DispStats; inference only."""
+        if not 0 <= t < len(self.archis):
+            raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
+        return self.net.forward_stats(left, right, t, self.archis[t], out=out, stats=stats)

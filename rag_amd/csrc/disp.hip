@@ -17,8 +17,46 @@ struct DispArgs {
   float sd, sh, sw;
 };
 
-template <class T>
-__global__ __launch_bounds__(256) void disp_softargmin_kernel(DispArgs a) {
+// Statistics of the softmin distribution p_k, formed in the pass that forms the disparity (the STATS = true instantiations; the
+// STATS = false ones are the plain kernels: same arithmetic, registers and occupancy).  Per output pixel, with e_k = 2^(x_k) the unnormalised
+// weights the kernels already hold (x_k <= 0 up to rounding) and s = sum e_k:
+//   variance = sum p_k (k - disp)^2 = M2 / s - (M1 / s)^2,  M1 = sum e_k (k - pv), M2 = sum e_k (k - pv)^2 about a pivot pv NEAR THE
+//              MODE.  The raw moment sum p k^2 - disp^2 subtracts two numbers of ~maxdisp^2 (6e-8 * 192^2 = 2e-3 px^2 of rounding, a
+//              percent of a trained network's 1 - 10 px^2); about the pivot both are of the size of the variance itself.
+//   peak     = max e_k / s
+//   entropy  = -sum p_k ln p_k = ln s - ln 2 * (sum e_k x_k) / s      (both terms >= 0: no cancellation)
+// stats: [B, 3, Ho, Wo] fp32, planes (variance, peak, entropy).
+struct DispMoments {
+  float pv = 0.f, m1 = 0.f, m2 = 0.f, xs = 0.f, pk = 0.f;
+  // Sample fd with weight e = 2^x.  M1 and M2 run in three short chains (the tiled kernels: one per fine sample of a coarse plane)
+  // that flush() folds into the totals every 8 coarse planes (the generic kernel: chain 0, every 16 samples).  On a BROAD distribution
+  // the pivot can sit ~100 px from the mean, M2 / s is then 4 x the variance, and one serial fp32 chain of 192 terms loses 1e-6 of it -
+  // the whole budget against ATen's pairwise sums; blocks of 8 terms and 8 block sums lose a third of that.  s and ws stay the serial
+  // chains of the plain kernel (same bits).
+  float b1[3] = {0.f, 0.f, 0.f}, b2[3] = {0.f, 0.f, 0.f};
+  __device__ __forceinline__ void add_chain(int j, float e, float x, float fd) {
+    const float t = fd - pv, et = e * t;
+    b1[j] += et;
+    b2[j] = fmaf(et, t, b2[j]);
+    xs = fmaf(e, x, xs);
+    pk = fmaxf(pk, e);
+  }
+  __device__ __forceinline__ void flush() {
+    m1 += (b1[0] + b1[1]) + b1[2];
+    m2 += (b2[0] + b2[1]) + b2[2];
+    b1[0] = b1[1] = b1[2] = b2[0] = b2[1] = b2[2] = 0.f;
+  }
+  __device__ __forceinline__ void store(float* stats, int64_t b, int64_t npix, int64_t o, float s) const {
+    const float c = m1 / s;                                              // disp - pv
+    float* const p = stats + b * 3 * npix + o;
+    p[0] = fmaxf(fmaf(-c, c, m2 / s), 0.f);
+    p[npix] = pk / s;
+    p[2 * npix] = fmaxf(fmaf(-0.6931471805599453f, xs / s, logf(s)), 0.f);
+  }
+};
+
+template <class T, bool STATS>
+__device__ __forceinline__ void disp_softargmin_body(const DispArgs& a, float* stats) {
   extern __shared__ float4 ztab[];                 // [maxdisp]
   for (int dd = threadIdx.x; dd < a.maxdisp; dd += 256) {
     const LinIdx lz = lin_index(dd, a.d, a.maxdisp, a.sd, 0);
@@ -55,6 +93,7 @@ __global__ __launch_bounds__(256) void disp_softargmin_kernel(DispArgs a) {
   int cz = 0;
   float b0 = plane(0), b1 = plane(a.d > 1 ? 1 : 0);
   float m = -INFINITY, s = 0.f, ws = 0.f;
+  DispMoments mo;
   for (int dd = 0; dd < a.maxdisp; ++dd) {
     const float4 tb = ztab[dd];                    // (i0, w0, w1 if i1 != i0 else 0, w1 if i1 == i0 else 0)
     const int i0 = (int)tb.x;
@@ -66,14 +105,45 @@ __global__ __launch_bounds__(256) void disp_softargmin_kernel(DispArgs a) {
     const float t = -fmaf(tb.y + tb.w, b0, tb.z * b1);
     // one of (m - m'), (t - m') is exactly 0 and 2^0 is exactly 1: ONE transcendental per sample, the same bits as two
     const bool up = t > m;                                   // the running maximum moves
-    const float x = __builtin_amdgcn_exp2f((up ? m - t : t - m) * K);   // 2^(-inf) = 0 on the first sample
+    const float xa = (up ? m - t : t - m) * K;
+    const float x = __builtin_amdgcn_exp2f(xa);              // 2^(-inf) = 0 on the first sample
     const float r = up ? x : 1.f, e = up ? 1.f : x;
+    if constexpr (STATS) {
+      // There is no pass 1 here, so the pivot follows the running maximum.  When it moves to this sample (weight 1, exponent 0, offset
+      // 0: it adds nothing to M1, M2, xs) the sums so far are re-centred about dd, re-based to the new maximum (every exponent drops
+      // by xa = log2 r) and rescaled by r like s and ws:
+      //   M2' = r (M2 - 2 dl M1 + dl^2 s),  M1' = r (M1 - dl s),  xs' = r (xs + xa s)      with dl = dd - pv and the OLD s.
+      // The rounding of a re-centring is relative to the moments about the new pivot, and r <= 1 shrinks it with them.
+      // Between moves the samples go into one block chain, folded into the totals every 16 samples and before a move (flush()):
+      // d = 213 -> 639 fine samples in one serial chain lost more than the gate allows on a broad distribution.
+      if (up) {
+        mo.flush();
+        const float dl = (float)dd - mo.pv;
+        mo.m2 = x * fmaf(dl, fmaf(dl, s, -2.f * mo.m1), mo.m2);
+        mo.m1 = x * fmaf(-dl, s, mo.m1);
+        mo.xs = s > 0.f ? x * fmaf(xa, s, mo.xs) : 0.f;      // first sample: xa = -inf, s = 0
+        mo.pv = (float)dd;
+        mo.pk = 1.f;
+      } else {
+        mo.add_chain(0, x, xa, (float)dd);
+      }
+      if ((dd & 15) == 15) mo.flush();
+    }
     s = fmaf(s, r, e);
     ws = fmaf(ws, r, e * (float)dd);
     m = up ? t : m;
   }
   a.out[(int64_t)b * npix + o] = ws / s;
+  if constexpr (STATS) {
+    mo.flush();
+    mo.store(stats, b, npix, o, s);
+  }
 }
+
+template <class T>
+__global__ __launch_bounds__(256) void disp_softargmin_kernel(DispArgs a) { disp_softargmin_body<T, false>(a, nullptr); }
+template <class T>
+__global__ __launch_bounds__(256) void disp_softargmin_stats_kernel(DispArgs a, float* stats) { disp_softargmin_body<T, true>(a, stats); }
 
 // The reference's own shape — maxdisp = 3 d and a 3x spatial upsampling (rag_model.py:40, 272-273) — as a tiled, two-pass kernel.
 //  * A workgroup owns 8 x 32 output pixels; the coarse cost block they interpolate from (d planes x 5 x 13 values) is staged through
@@ -90,8 +160,8 @@ __global__ __launch_bounds__(256) void disp_softargmin_kernel(DispArgs a) {
 //    fmaf(w0, b0, w1 * b1).
 constexpr int DX3_TY = 8, DX3_TX = 32, DX3_CR = 5, DX3_CC = 13, DX3_CP = DX3_CR * DX3_CC;
 
-template <class T>
-__global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) {
+template <class T, bool STATS>
+__device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float* stats) {
   extern __shared__ __attribute__((aligned(16))) float dx3_lds[];
   float4* const ztab = reinterpret_cast<float4*>(dx3_lds);            // [maxdisp] (wp, wc, wn, dd)
   float* const tile = dx3_lds + 4 * a.maxdisp;                        // [d][5][13]
@@ -137,6 +207,10 @@ __global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) {
   };
   constexpr float K = 1.4426950408889634f;
   float s = 0.f, ws = 0.f;
+  // STATS: the coarse arg-min of pass 1 gives the pivot of the moments, fine sample 3 argmin + 1 (the one whose source index IS that
+  // plane); the softmin's mode is within a coarse step of it
+  DispMoments mo;
+  int am = 0;
   // d = 64 (maxdisp 192, the reference's only configuration, rag_model.py:274): the 64 plane samples of pass 1 stay in REGISTERS for
   // pass 2 — no second round of 4 d LDS reads and bilinear arithmetic (same operations on the same values: identical bits).  Chunks
   // of 8 planes fenced by sched_barrier: unfenced, the scheduler hoisted all 256 operand reads and the kernel spilled or ran at
@@ -150,6 +224,12 @@ __global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) {
       lo = fminf(lo, v[z]);
       if ((z & 7) == 7) __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (STATS) {    // the arg-min from the FINAL minimum: tracked inside the loop above, every running minimum stayed live (142 VGPRs)
+#pragma unroll
+      for (int z = 63; z >= 0; --z) am = v[z] == lo ? z : am;
+      mo.pv = (float)(3 * am + 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
       const float vp_ = v[k > 0 ? k - 1 : 0], vc_ = v[k], vn_ = v[k < 63 ? k + 1 : 63];
@@ -157,16 +237,26 @@ __global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) {
       for (int j = 0; j < 3; ++j) {
         const float4 tb = ztab[3 * k + j];
         const float c = fmaf(tb.x, vp_, fmaf(tb.y, vc_, tb.z * vn_));
-        const float e = __builtin_amdgcn_exp2f((lo - c) * K);
+        const float x = (lo - c) * K;
+        const float e = __builtin_amdgcn_exp2f(x);
         s += e;
         ws = fmaf(e, tb.w, ws);
+        if constexpr (STATS) mo.add_chain(j, e, x, tb.w);
       }
-      if ((k & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+      if ((k & 7) == 7) {
+        if constexpr (STATS) mo.flush();
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
   } else {
   float lo = INFINITY;
 #pragma clang loop unroll_count(4) vectorize(disable)
-  for (int z = 0; z < D; ++z) lo = fminf(lo, plane(z));
+  for (int z = 0; z < D; ++z) {
+    const float vz = plane(z);
+    if constexpr (STATS) am = vz < lo ? z : am;
+    lo = fminf(lo, vz);
+  }
+  if constexpr (STATS) mo.pv = (float)(3 * am + 1);
   // exponent of a sample: (min - cost) * K: the difference is formed BEFORE the scaling by K, like the generic kernel, so large
   // |cost| does not lose the bits that matter near the minimum
   float vc = plane(0), vp = vc, vn = plane(min(1, D - 1));
@@ -175,15 +265,27 @@ __global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) {
     for (int j = 0; j < 3; ++j) {
       const float4 tb = ztab[3 * k + j];     // wave-uniform address: one broadcast read
       const float c = fmaf(tb.x, vp, fmaf(tb.y, vc, tb.z * vn));
-      const float e = __builtin_amdgcn_exp2f((lo - c) * K);
+      const float x = (lo - c) * K;
+      const float e = __builtin_amdgcn_exp2f(x);
       s += e;
       ws = fmaf(e, tb.w, ws);
+      if constexpr (STATS) mo.add_chain(j, e, x, tb.w);
     }
     vp = vc; vc = vn; vn = plane(min(k + 2, D - 1));
+    if constexpr (STATS) if ((k & 7) == 7) mo.flush();
   }
+  if constexpr (STATS) mo.flush();
   }
-  if (ox0 + tx < a.Wo && oy0 + ty < a.Ho) a.out[(int64_t)b * a.Ho * a.Wo + (int64_t)oy * a.Wo + ox] = ws / s;
+  if (ox0 + tx < a.Wo && oy0 + ty < a.Ho) {
+    a.out[(int64_t)b * a.Ho * a.Wo + (int64_t)oy * a.Wo + ox] = ws / s;
+    if constexpr (STATS) mo.store(stats, b, (int64_t)a.Ho * a.Wo, (int64_t)oy * a.Wo + ox, s);
+  }
 }
+
+template <class T>
+__global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) { disp_softargmin_x3_body<T, false>(a, nullptr); }
+template <class T>
+__global__ __launch_bounds__(256) void disp_softargmin_x3_stats_kernel(DispArgs a, float* stats) { disp_softargmin_x3_body<T, true>(a, stats); }
 
 // The wavefront-reduction form north_star names, for the same configuration (maxdisp = 3 d, 3x upsampling): 16 lanes share one
 // output pixel, lane l owns the coarse planes 4l .. 4l+3 (d <= 64) and their 12 fine samples; a wave step is 4 pixels.
@@ -295,6 +397,39 @@ __global__ __launch_bounds__(256) void disparity_regression_kernel(const T* __re
   out[(int64_t)b * hw + o] = acc;
 }
 
+// DisparityRegression with the statistics of `prob`, taken as given (not renormalised): out as above (the same fmaf chain, the same
+// bits), variance = sum p (k - out)^2 by the definition in a second walk over the D planes (a one-hot prob gives exactly 0: out is
+// exactly its index), peak = max p, entropy = -sum_{p > 0} p ln p.  The two stat sums run in 8 interleaved partial sums: there is no
+// interpolation error to hide behind here, and a serial fp32 sum of 192 terms alone is ~5e-7 of the result.
+template <class T>
+__global__ __launch_bounds__(256) void disparity_regression_stats_kernel(const T* __restrict__ prob, float* __restrict__ out,
+                                                                        float* __restrict__ stats, int D, int64_t hw) {
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= hw) return;
+  const int b = blockIdx.y;
+  const T* p = prob + (int64_t)b * D * hw + o;
+  float acc = 0.f;
+#pragma unroll 8
+  for (int dd = 0; dd < D; ++dd) acc = fmaf(ld(p + (int64_t)dd * hw), (float)dd, acc);
+  float var[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ent[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pk = 0.f;
+  for (int d0 = 0; d0 < D; d0 += 8) {
+    static_for<8>([&](auto J) {
+      constexpr int j = decltype(J)::value;
+      if (d0 + j < D) {
+        const float q = ld(p + (int64_t)(d0 + j) * hw), t = (float)(d0 + j) - acc;
+        var[j] = fmaf(q * t, t, var[j]);
+        ent[j] = q > 0.f ? fmaf(q, logf(q), ent[j]) : ent[j];
+        pk = fmaxf(pk, q);
+      }
+    });
+  }
+  out[(int64_t)b * hw + o] = acc;
+  float* const st = stats + (int64_t)b * 3 * hw + o;
+  st[0] = ((var[0] + var[1]) + (var[2] + var[3])) + ((var[4] + var[5]) + (var[6] + var[7]));
+  st[hw] = pk;
+  st[2 * hw] = 0.f - (((ent[0] + ent[1]) + (ent[2] + ent[3])) + ((ent[4] + ent[5]) + (ent[6] + ent[7])));
+}
+
 }  // namespace ragmi
 
 extern "C" int ragmi_disp_softargmin_fwd(const void* cost, void* out, int B, int d, int h, int w, int maxdisp, int Ho,
@@ -345,4 +480,49 @@ extern "C" int ragmi_disparity_regression_fwd(const void* prob, void* out, int B
   else
     hipLaunchKernelGGL(disparity_regression_kernel<float>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), (const float*)prob, (float*)out, D, hw);
   return check_launch("disparity_regression");
+}
+
+// The statistics launches: the argument checks, the dispatch rule and the launch geometry of the plain entry points above, one launch each.
+extern "C" int ragmi_disp_softargmin_stats_fwd(const void* cost, void* out, void* stats, int B, int d, int h, int w, int maxdisp,
+                                               int Ho, int Wo, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(cost && out && stats, RAGMI_EINVAL, "disp_softargmin_stats: null pointer");
+  RAGMI_REQUIRE(B > 0 && d > 0 && h > 0 && w > 0 && maxdisp > 0 && Ho > 0 && Wo > 0, RAGMI_EINVAL,
+                "disp_softargmin_stats: non-positive size");
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "disp_softargmin_stats: dtype %d not built", dtype);
+  RAGMI_REQUIRE(B <= 65535 && (int64_t)h * w < (1ll << 30), RAGMI_EUNSUPPORTED, "disp_softargmin_stats: size too large");
+  DispArgs a{cost, (float*)out, d, h, w, maxdisp, Ho, Wo,
+             lin_scale(d, maxdisp, 0), lin_scale(h, Ho, 0), lin_scale(w, Wo, 0)};
+  float* const st = (float*)stats;
+  const hipStream_t q = static_cast<hipStream_t>(stream);
+  dim3 grid((unsigned)ceil_div((int64_t)Ho * Wo, 256), B);
+  const size_t lds = (size_t)maxdisp * sizeof(float4);
+  RAGMI_REQUIRE(lds <= 64 * 1024, RAGMI_EUNSUPPORTED, "disp_softargmin_stats: maxdisp %d exceeds the tap table (4096)", maxdisp);
+  const size_t lds3 = lds + (size_t)d * DX3_CP * sizeof(float);
+  if (maxdisp == 3 * d && Ho == 3 * h && Wo == 3 * w && lds3 <= 64 * 1024) {   // the tiled form (register form at d = 64, else the rolling window)
+    const dim3 g3((unsigned)ceil_div(Wo, DX3_TX), (unsigned)ceil_div(Ho, DX3_TY), (unsigned)B);
+    const dim3 g1((unsigned)(ceil_div((int64_t)g3.x * g3.y, 8) * 8), 1, (unsigned)B);
+    if (dtype == RAGMI_BF16) hipLaunchKernelGGL(disp_softargmin_x3_stats_kernel<bf16_t>, g1, dim3(256), lds3, q, a, st);
+    else hipLaunchKernelGGL(disp_softargmin_x3_stats_kernel<float>, g1, dim3(256), lds3, q, a, st);
+    return check_launch("disp_softargmin_stats");
+  }
+  if (dtype == RAGMI_BF16) hipLaunchKernelGGL(disp_softargmin_stats_kernel<bf16_t>, grid, dim3(256), lds, q, a, st);
+  else hipLaunchKernelGGL(disp_softargmin_stats_kernel<float>, grid, dim3(256), lds, q, a, st);
+  return check_launch("disp_softargmin_stats");
+}
+
+extern "C" int ragmi_disparity_regression_stats_fwd(const void* prob, void* out, void* stats, int B, int D, int H, int W, int dtype,
+                                                    void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(prob && out && stats, RAGMI_EINVAL, "disparity_regression_stats: null pointer");
+  RAGMI_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, RAGMI_EINVAL, "disparity_regression_stats: non-positive size");
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "disparity_regression_stats: dtype %d not built", dtype);
+  RAGMI_REQUIRE(B <= 65535, RAGMI_EUNSUPPORTED, "disparity_regression_stats: B too large");
+  const int64_t hw = (int64_t)H * W;
+  dim3 grid((unsigned)ceil_div(hw, 256), B);
+  if (dtype == RAGMI_BF16)
+    hipLaunchKernelGGL(disparity_regression_stats_kernel<bf16_t>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), (const bf16_t*)prob, (float*)out, (float*)stats, D, hw);
+  else
+    hipLaunchKernelGGL(disparity_regression_stats_kernel<float>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), (const float*)prob, (float*)out, (float*)stats, D, hw);
+  return check_launch("disparity_regression_stats");
 }

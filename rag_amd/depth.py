@@ -358,6 +358,13 @@ class Network(_StereoNetwork):
         y6 = self._trunk(x, self.stem3d0[selected_ops[8]], self.stem3d1[selected_ops[9]], cells, self.last_6_3d[t], self.last_12_3d[t])
         return self._head(y6, x.shape[2:], self.last_3_3d[t])
 
+    def forward_stats(self, *args, **kwargs):
+        """The stereo head's statistics do not exist here: the depth head is a sigmoid of one value per pixel, not a distribution."""
+        raise NotImplementedError("rag_amd.depth.Network: forward_stats belongs to the stereo head (a softmin over disparities); "
+                                  "the depth head has no distribution")
+
+    search_forward_stats = forward_stats
+
     def search_forward_train(self, left, t, selected_ops):         # rag_model.py:716-740 under autograd (approaches/rag.py:405)
         """The training forward of a sampled path: `search_forward` on the composition of `forward_train`, -> depth [B, 3h, 3w] with
         an autograd graph.  The module modes are the caller's (`search_mode()`: the trunk's BatchNorms on running statistics, the

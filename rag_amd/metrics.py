@@ -85,6 +85,66 @@ def stereo_metrics(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float
         return StereoMetrics(_raw(disp_est.detach(), disp_gt, maxdisp, meter))
 
 
+# --------------------------------------------------------------------------- per-pixel statistics of the disparity distribution
+STAT_NAMES = ("variance", "peak", "entropy")
+
+
+class DispStats:
+    """Result of a `forward_stats` call: `.disp` [B,H,W] is the disparity (the bits of the plain forward), `.tensor` [B,3,H,W] the
+    statistics of the softmin distribution it is the mean of; `.variance` (px^2), `.peak` (max_k p_k) and `.entropy` (nats) are
+    views of its planes.  Everything stays on the device."""
+
+    def __init__(self, disp: torch.Tensor, tensor: torch.Tensor):
+        self.disp = disp
+        self.tensor = tensor
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        return self.tensor[:, STAT_NAMES.index(name)]
+
+    @property
+    def variance(self) -> torch.Tensor:
+        return self.tensor[:, 0]
+
+    @property
+    def peak(self) -> torch.Tensor:
+        return self.tensor[:, 1]
+
+    @property
+    def entropy(self) -> torch.Tensor:
+        return self.tensor[:, 2]
+
+
+def refuse_autograd(what: str, *ts) -> None:
+    """The statistics launches have no backward: refuse an input that autograd would track."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(f"rag_amd {what}: inference only (the statistics have no backward and the call would drop the input's "
+                           "autograd graph); call it under torch.no_grad() or on detached inputs")
+
+
+def prob_stats_torch(prob: torch.Tensor):
+    """(disp [B,H,W], stats [B,3,H,W]) of a distribution prob[B,D,H,W] over the disparity axis, taken as given, in prob's dtype and
+    on its device: disp = sum p k, variance = sum p (k - disp)^2 (the centred second moment), peak = max p, entropy = -sum p ln p
+    with terms of p <= 0 contributing 0."""
+    k = torch.arange(prob.shape[1], dtype=prob.dtype, device=prob.device).view(1, -1, 1, 1)
+    disp = (prob * k).sum(1)
+    var = (prob * (k - disp[:, None]) ** 2).sum(1)
+    pos = prob > 0
+    ent = -(torch.where(pos, prob, torch.ones_like(prob)).log() * prob * pos).sum(1)
+    return disp, torch.stack((var, prob.max(1).values, ent), dim=1)
+
+
+def disp_stats_torch(cost: torch.Tensor, maxdisp: int, size=None):
+    """Plain-torch twin of ops.disp_softargmin_stats in cost's dtype and on its device (the CPU path, and the float64 / ATen yardstick
+    of the tests and tools/bench_disp_stats.py): cost [B,1,d,h,w] or [B,d,h,w] -> F.interpolate to (maxdisp, *size) (trilinear,
+    align_corners=False; size defaults to (3h, 3w)) -> softmin over the disparity axis -> prob_stats_torch.  Returns (disp, stats)."""
+    import torch.nn.functional as F
+    if cost.dim() == 4:
+        cost = cost[:, None]
+    Ho, Wo = (3 * cost.shape[3], 3 * cost.shape[4]) if size is None else size
+    v = F.interpolate(cost, (int(maxdisp), int(Ho), int(Wo)), mode="trilinear", align_corners=False)[:, 0]
+    return prob_stats_torch(F.softmin(v, dim=1))
+
+
 class MaskedSmoothL1Fn(torch.autograd.Function):
     """F.smooth_l1_loss(disp_est[mask], disp_gt[mask]) with mask = 0 < gt < maxdisp (rag.py:210-211), forward and
     backward in one kernel each, without the boolean gather (no stream synchronisation)."""

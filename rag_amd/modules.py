@@ -28,6 +28,7 @@ import torch.nn as nn
 
 from . import autograd as ag
 from . import ops
+from .metrics import DispStats, refuse_autograd
 
 # src/automl/genotypes_2d.py:4-8 — the genotype handed to Network / Cell_3d; 3-D cells read `.reduce`
 Genotype = namedtuple("Genotype_2D", "normal normal_concat reduce reduce_concat")
@@ -310,6 +311,12 @@ class DisparityRegression(nn.Module):
             return ag.DispRegFn.apply(x, self.maxdisp)
         return ops.disparity_regression(x, self.maxdisp)
 
+    def forward_stats(self, x, out=None, stats=None):
+        """forward with the statistics of x's disparity axis in the same launch -> DispStats; inference only."""
+        assert x.is_contiguous() is True
+        refuse_autograd("DisparityRegression.forward_stats", x)
+        return DispStats(*ops.disparity_regression_stats(x, self.maxdisp, out, stats))
+
 
 class Disp(nn.Module):
     """src/models/rag_model.py:32-44, fused: trilinear x3 (align_corners=False) -> Softmin -> regression."""
@@ -324,6 +331,12 @@ class Disp(nn.Module):
         if ag.needs_grad(x):
             return ag.DispFn.apply(x, self.maxdisp)
         return ops.disp_softargmin(x, self.maxdisp)
+
+    def forward_stats(self, x, out=None, stats=None):
+        """forward with the per-pixel variance, peak and entropy of the softmin distribution in the same launch -> DispStats
+        (.disp is forward's result bit for bit); inference only.  `out` / `stats`: caller-owned outputs (a captured graph's)."""
+        refuse_autograd("Disp.forward_stats", x)
+        return DispStats(*ops.disp_softargmin_stats(x, self.maxdisp, out, stats))
 
 
 def _scale_dimension(dim, scale):
@@ -1104,3 +1117,14 @@ class MatchingNet(nn.Module):
         # remains available and gives the same result
         cost = self.matching(None, task_arch, None, features=(left_fea, right_fea))
         return self.disp(cost)
+
+    def forward_stats(self, left_fea, right_fea, task_arch=None, out=None, stats=None):
+        """forward with the head's statistics launch in place of the plain one -> DispStats; inference only."""
+        refuse_autograd("MatchingNet.forward_stats", left_fea, right_fea)
+        if task_arch is None:
+            task_arch = self.arch_init
+        if left_fea.shape != right_fea.shape or left_fea.dim() != 4:
+            raise ValueError("MatchingNet: left/right features must both be [B, C, h, w]")
+        with torch.no_grad():
+            cost = self.matching(None, task_arch, None, features=(left_fea, right_fea))
+            return self.disp.forward_stats(cost, out, stats)

@@ -19,6 +19,7 @@ from typing import Dict, List
 import torch
 import torch.nn as nn
 
+from .metrics import refuse_autograd
 from .modules import Cell_2d, Cell_3d, ConvBR_2d, ConvBR_3d, MatchingNet, _ConvBR  # noqa: F401
 
 # Feature-Net macro architecture, rag_model.py:207-219: (prev_prev_fm, prev_fm, filter_multiplier, downup)
@@ -155,6 +156,23 @@ class Network(MatchingNet):
         lf, rf = self._features(left, right, lambda x: self.search_feature(x, selected_ops))
         cost = self.search_matching(None, selected_ops, t, features=(lf, rf))
         return self.disp(cost)
+
+    def forward_stats(self, left, right, t, task_arch=None, path=None, out=None, stats=None):
+        """forward with the head's statistics launch in place of the plain one -> DispStats (.disp is forward's result bit for
+        bit, .variance / .peak / .entropy describe the distribution it is the mean of); inference only."""
+        refuse_autograd("Network.forward_stats", left, right)
+        with torch.no_grad():
+            lf, rf = self._features(left, right, lambda x: self.feature(x, task_arch, path))
+            cost = self.matching(None, task_arch, path, features=(lf, rf))
+            return self.disp.forward_stats(cost, out, stats)
+
+    def search_forward_stats(self, left, right, t, selected_ops, out=None, stats=None):
+        """search_forward with the head's statistics launch -> DispStats; inference only."""
+        refuse_autograd("Network.search_forward_stats", left, right)
+        with torch.no_grad():
+            lf, rf = self._features(left, right, lambda x: self.search_feature(x, selected_ops))
+            cost = self.search_matching(None, selected_ops, t, features=(lf, rf))
+            return self.disp.forward_stats(cost, out, stats)
 
     # ------------------------------------------------------------------ the unit search's step (Appr.search_epoch, rag.py:344-406)
     def search_mode(self):

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -795,6 +795,51 @@ def disparity_regression(prob: torch.Tensor, maxdisp: int) -> torch.Tensor:
     check(load_library().ragmi_disparity_regression_fwd(prob.data_ptr(), out.data_ptr(), B, D, H, W, dt, _stream()),
           "disparity_regression")
     return out
+
+
+def _stats_outputs(what: str, ref: torch.Tensor, B: int, H: int, W: int, out, stats):
+    """The two fp32 outputs of a statistics launch: fresh, or the caller's own (a captured graph owns its outputs)."""
+    if out is None:
+        out = torch.empty((B, H, W), device=ref.device, dtype=torch.float32)
+    if stats is None:
+        stats = torch.empty((B, 3, H, W), device=ref.device, dtype=torch.float32)
+    _need_gpu(out, stats)
+    if tuple(out.shape) != (B, H, W) or tuple(stats.shape) != (B, 3, H, W) or not out.is_contiguous() or not stats.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous [{B}, {H}, {W}] and stats a contiguous [{B}, 3, {H}, {W}] fp32 tensor")
+    if out.device != ref.device or stats.device != ref.device:
+        raise ValueError(f"{what}: out and stats must be on the input's device")
+    return out, stats
+
+
+def disp_softargmin_stats(cost: torch.Tensor, maxdisp: int, out: Optional[torch.Tensor] = None,
+                          stats: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """disp_softargmin with the per-pixel statistics of the softmin distribution, one launch: cost[B,1,d,h,w] (or [B,d,h,w]) ->
+    (disparity [B,3h,3w] - the bits of disp_softargmin, stats [B,3,3h,3w] = variance px^2, peak, entropy nats).  Inference only."""
+    dt = _act(cost)
+    if cost.dim() == 5:
+        if cost.shape[1] != 1:
+            raise ValueError("disp_softargmin_stats: expected a single-channel cost volume")
+        cost = cost[:, 0]
+    cost = cost.contiguous()
+    B, d, h, w = cost.shape
+    out, stats = _stats_outputs("disp_softargmin_stats", cost, B, 3 * h, 3 * w, out, stats)
+    check(load_library().ragmi_disp_softargmin_stats_fwd(cost.data_ptr(), out.data_ptr(), stats.data_ptr(), B, d, h, w, int(maxdisp),
+                                                         3 * h, 3 * w, dt, _stream()), "disp_softargmin_stats")
+    return out, stats
+
+
+def disparity_regression_stats(prob: torch.Tensor, maxdisp: int, out: Optional[torch.Tensor] = None,
+                               stats: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """disparity_regression with the statistics of prob[B,D,H,W] taken as given (not renormalised): (out [B,H,W], stats [B,3,H,W])."""
+    dt = _act(prob)
+    assert prob.is_contiguous()
+    B, D, H, W = prob.shape
+    if D != maxdisp:
+        raise ValueError("disparity_regression_stats: prob.shape[1] must equal maxdisp")
+    out, stats = _stats_outputs("disparity_regression_stats", prob, B, H, W, out, stats)
+    check(load_library().ragmi_disparity_regression_stats_fwd(prob.data_ptr(), out.data_ptr(), stats.data_ptr(), B, D, H, W, dt,
+                                                              _stream()), "disparity_regression_stats")
+    return out, stats
 
 
 # ------------------------------------------------------------------------------------------------------------------
