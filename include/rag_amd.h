@@ -559,6 +559,41 @@ int ragmi_costvol_bwd(const void* dcost, void* dleft, void* dright, int B, int C
 int ragmi_disp_softargmin_bwd(const void* cost, const void* dout, void* dcost, int B, int d, int h, int w,
                               int maxdisp, int Ho, int Wo, void* stream);
 
+/*
+ * Adjoint of ragmi_disp_softargmin_stats_fwd (rag_model.py:18-44 under autograd, with the statistics as further outputs).
+ * With v_k the fine cost of a pixel, p = softmin(v), mu = sum p_k k, var = sum p_k (k - mu)^2, H = -sum p_k ln p_k,
+ * k* = argmax p (the first sample that holds the maximum), peak = p_k*, and the cotangents gmu = dout, (gV, gP, gH) = dstats:
+ *   dL/dv_k = -p_k [ gmu (k - mu) + gV ((k - mu)^2 - var) - gH (ln p_k + H) - gP peak ] - [k = k*] gP peak
+ * scattered through the trilinear taps into dcost.  The clamps of variance and entropy at 0 are treated as the identity.
+ * cost, dcost: [B,d,h,w] fp32; dout: [B,Ho,Wo] fp32 or NULL; dstats: [B,3,Ho,Wo] fp32 (variance, peak, entropy) or NULL.  A NULL
+ * cotangent is a zero one (the same bits); both NULL is RAGMI_EINVAL.  Same contract as ragmi_disp_softargmin_bwd: dcost is
+ * pre-zeroed by the caller and added to with float atomics (one add per 16 x 16 fine tile, coarse cell and plane), Ho = 3h, Wo = 3w
+ * and maxdisp <= 3072, else RAGMI_EUNSUPPORTED; sizes <= 0 or B > 65535 are RAGMI_EINVAL.  Every argument is checked before the
+ * launch.  One launch; no allocation, synchronisation, memset or memcpy.  The softmin statistics are recomputed from cost.
+ */
+int ragmi_disp_softargmin_stats_bwd(const void* cost, const void* dout, const void* dstats, void* dcost, int B, int d, int h, int w,
+                                    int maxdisp, int Ho, int Wo, void* stream);
+
+/*
+ * Uncertainty-aware regression loss over the head's own variance (Kendall & Gal's form; the reference trains the mean only,
+ * approaches/rag.py:210-211).  mask = 0 < gt < maxdisp, s = stats[:,0] + var_floor, per masked pixel
+ *   l = smooth_l1(est - gt) * rsqrt(s) + 0.5 ln s                      (smooth-L1 with beta = 1)
+ * out[0] = sum l / N, out[1] = the masked smooth-L1 mean (out[0] of ragmi_stereo_metrics_fwd, for logging), out[2] = the mean of
+ * sqrt(s) over the mask, out[3] = N.  An empty mask gives 0 / 0 (NaN) in out[0..2], as ragmi_stereo_metrics_fwd's out[0].
+ * disp_est, disp_gt: [B,H,W] fp32; stats: [B,3,H,W] fp32 (plane 0 is read); acc: ragmi_uncertainty_loss_workspace_elems(B,H,W)
+ * floats of scratch (nothing to zero); out: 4 floats.  var_floor > 0 (RAGMI_EINVAL otherwise).  Two launches; no atomics, no
+ * memset, no synchronisation; bitwise reproducible (fixed-order two-level sum, the second level in double).
+ */
+int64_t ragmi_uncertainty_loss_workspace_elems(int B, int H, int W);
+int ragmi_uncertainty_loss_fwd(const void* disp_est, const void* stats, const void* disp_gt, int B, int H, int W, float maxdisp,
+                               float var_floor, void* acc, void* out, void* stream);
+
+/* gradient of out[0], one launch: ddisp[B,H,W] = gout[0] [mask] clamp(est - gt, -1, 1) rsqrt(s) / out[3] and ALL THREE planes of
+ * dstats[B,3,H,W]: plane 0 = gout[0] [mask] (0.5 / s - 0.5 smooth_l1 s^(-3/2)) / out[3], planes 1 and 2 = 0 (written here so that
+ * no memset enters a captured step).  out: the forward's 4 floats; gout: 1 float on the device. */
+int ragmi_uncertainty_loss_bwd(const void* disp_est, const void* stats, const void* disp_gt, const void* out, const void* gout,
+                               void* ddisp, void* dstats, int B, int H, int W, float maxdisp, float var_floor, void* stream);
+
 /* backward of ragmi_conv2d_k3_strided_fwd's convolution (Feature-Net stem, operations_2d.py ConvBR_2d stride 3):
  * dx[B,Cin,H,W] from g[B,Cout,Ho,Wo];  dw[Cout,Cin,3,3] (+=) */
 int ragmi_conv2d_k3_strided_dgrad(const void* g, const void* weight, void* dx, int B, int Cin, int Cout, int H, int W, int stride,

@@ -14,6 +14,7 @@ batch-norm, interpolate or softmax runs: if the library is missing these raise, 
     TrilinearFn   F.interpolate(mode='trilinear') and its scatter adjoint
     CostVolFn     the concat-and-shift cost volume and its gather adjoint
     DispFn        fused upsample x3 -> softmin -> expectation and its adjoint
+    DispStatsFn   the same with the distribution's variance, peak and entropy as a second output, and the adjoint of all four
     AddFn         sum of two branch outputs
 
 Per-channel BatchNorm bookkeeping (mean/var -> scale/shift, the three backward coefficients, running-stat
@@ -332,6 +333,28 @@ class DispFn(torch.autograd.Function):
     def backward(ctx, dout):
         (cost,) = ctx.saved_tensors
         return ops.disp_softargmin_bwd(cost, dout, ctx.maxdisp), None
+
+
+class DispStatsFn(torch.autograd.Function):
+    """Disp.forward_train_stats: the statistics launch (disparity and [variance, peak, entropy]) under autograd.  An output nobody
+    differentiates arrives as None (set_materialize_grads(False)) and goes to the adjoint as a NULL pointer; without a cotangent of
+    the statistics the backward is DispFn's own launch (the same bits)."""
+
+    @staticmethod
+    def forward(ctx, cost, maxdisp):
+        ctx.save_for_backward(cost)
+        ctx.maxdisp = maxdisp
+        ctx.set_materialize_grads(False)
+        return ops.disp_softargmin_stats(cost, maxdisp)
+
+    @staticmethod
+    def backward(ctx, dout, dstats):
+        (cost,) = ctx.saved_tensors
+        if dout is None and dstats is None:
+            return None, None
+        if dstats is None:
+            return ops.disp_softargmin_bwd(cost, dout, ctx.maxdisp), None
+        return ops.disp_softargmin_stats_bwd(cost, dout, dstats, ctx.maxdisp), None
 
 
 class AddFn(torch.autograd.Function):

@@ -364,6 +364,7 @@ class Network(_StereoNetwork):
                                   "the depth head has no distribution")
 
     search_forward_stats = forward_stats
+    forward_train_stats = forward_stats
 
     def search_forward_train(self, left, t, selected_ops):         # rag_model.py:716-740 under autograd (approaches/rag.py:405)
         """The training forward of a sampled path: `search_forward` on the composition of `forward_train`, -> depth [B, 3h, 3w] with

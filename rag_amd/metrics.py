@@ -174,6 +174,79 @@ def masked_smooth_l1(disp_est: torch.Tensor, disp_gt: torch.Tensor, maxdisp: flo
     return MaskedSmoothL1Fn.apply(disp_est, disp_gt, maxdisp, meter)
 
 
+# --------------------------------------------------------------------------- training the head's uncertainty
+VAR_FLOOR = 1.0 / 12.0       # px^2: the variance of a uniform distribution over one disparity bin; a parameter, not a measurement
+
+
+def disp_stats_bwd_torch(cost: torch.Tensor, maxdisp: int, dout: Optional[torch.Tensor], dstats: Optional[torch.Tensor]) -> torch.Tensor:
+    """Plain-torch twin of ops.disp_softargmin_stats_bwd in cost's dtype and on its device: the closed form
+        dL/dv_k = -p_k [ gmu (k - mu) + gV ((k - mu)^2 - var) - gH (ln p_k + H) - gP peak ] - [k = k*] gP peak
+    on the upsampled cost v (p = softmin(v), k* = the first arg-max), then the adjoint of the trilinear x3 upsample (linear: ATen's
+    own).  cost [B,1,d,h,w] or [B,d,h,w]; dout [B,3h,3w] or None; dstats [B,3,3h,3w] (variance, peak, entropy) or None."""
+    import torch.nn.functional as F
+    shape = cost.shape
+    c = (cost if cost.dim() == 5 else cost[:, None]).detach().clone().requires_grad_(True)
+    Ho, Wo = 3 * c.shape[3], 3 * c.shape[4]
+    with torch.enable_grad():
+        v = F.interpolate(c, (int(maxdisp), Ho, Wo), mode="trilinear", align_corners=False)
+    with torch.no_grad():
+        logp = F.log_softmax(-v[:, 0], dim=1)
+        p = logp.exp()
+        zero = torch.zeros((), dtype=c.dtype, device=c.device)
+        gmu = dout[:, None].to(c.dtype) if dout is not None else zero
+        gV, gP, gH = (dstats[:, i:i + 1].to(c.dtype) for i in range(3)) if dstats is not None else (zero, zero, zero)
+        k = torch.arange(int(maxdisp), dtype=c.dtype, device=c.device).view(1, -1, 1, 1)
+        u = k - (p * k).sum(1, keepdim=True)
+        var = (p * u * u).sum(1, keepdim=True)
+        ent = -(p * logp).sum(1, keepdim=True)
+        peak, kstar = p.max(1, keepdim=True)
+        gv = -p * (gmu * u + gV * (u * u - var) - gH * (logp + ent) - gP * peak)
+        gv = gv - torch.zeros_like(p).scatter_(1, kstar, 1.0) * (gP * peak)
+    (g,) = torch.autograd.grad(v, c, gv[:, None])
+    return g.reshape(shape)
+
+
+def uncertainty_loss_torch(disp: torch.Tensor, stats: torch.Tensor, gt: torch.Tensor, maxdisp: float, var_floor: float = VAR_FLOOR) -> torch.Tensor:
+    """Plain-torch twin of uncertainty_loss in disp's dtype and on its device (differentiable in disp and stats): the mean over
+    mask = 0 < gt < maxdisp of smooth_l1(disp - gt) * rsqrt(s) + 0.5 ln s with s = stats[:, 0] + var_floor; nan on an empty mask."""
+    import torch.nn.functional as F
+    mask = (gt > 0) & (gt < maxdisp)
+    s = stats[:, 0] + var_floor
+    per = F.smooth_l1_loss(disp, gt.to(disp.dtype), reduction="none") * torch.rsqrt(s) + 0.5 * torch.log(s)
+    return torch.where(mask, per, torch.zeros_like(per)).sum() / mask.sum()
+
+
+class UncertaintyLossFn(torch.autograd.Function):
+    """The uncertainty-aware loss of the head's own variance: one fused forward (two launches, no atomics) and a one-launch backward
+    that writes d loss / d disp and all three planes of d loss / d stats."""
+
+    @staticmethod
+    def forward(ctx, disp_est, stats, disp_gt, maxdisp, var_floor):
+        est, st, gt = disp_est.contiguous(), stats.contiguous(), disp_gt.contiguous()
+        out = ops.uncertainty_loss_fwd(est, st, gt, maxdisp, var_floor)
+        ctx.save_for_backward(est, st, gt, out)
+        ctx.maxdisp, ctx.var_floor = float(maxdisp), float(var_floor)
+        return out[0] * 1.0          # a kernel, not a memcpy node (as MaskedSmoothL1Fn)
+
+    @staticmethod
+    def backward(ctx, gout):
+        est, st, gt, out = ctx.saved_tensors
+        gout = gout.reshape(1).contiguous().float()
+        ddisp, dstats = ops.uncertainty_loss_bwd(est, st, gt, out, gout, ctx.maxdisp, ctx.var_floor)
+        return ddisp, dstats, None, None, None
+
+
+def uncertainty_loss(disp: torch.Tensor, stats: torch.Tensor, gt: torch.Tensor, maxdisp: float = 192, var_floor: float = VAR_FLOOR) -> torch.Tensor:
+    """Uncertainty-aware regression loss (Kendall & Gal's form) over the head's own variance: disp [B,H,W] and stats [B,3,H,W] of a
+    forward_train_stats call (DispStats.disp / .tensor), gt [B,H,W].  Per pixel of mask = 0 < gt < maxdisp, with
+    s = stats[:, 0] + var_floor:  smooth_l1(disp - gt) * rsqrt(s) + 0.5 ln s, averaged over the mask.  A residual the network marks
+    as uncertain costs less, and marking it costs ln sigma.  Differentiable in disp and stats (HIP, fp32); on CPU tensors the
+    plain-torch twin runs.  ops.uncertainty_loss_fwd gives the logging vector (loss, smooth-L1 mean, mean sigma, N)."""
+    if not disp.is_cuda:
+        return uncertainty_loss_torch(disp, stats, gt, maxdisp, var_floor)
+    return UncertaintyLossFn.apply(disp, stats, gt, maxdisp, var_floor)
+
+
 # --------------------------------------------------------------------------- self-supervised loss (src_self, supervise=False)
 SELFSUP_NAMES = ("loss", "ssim", "l1", "smooth")
 

@@ -338,6 +338,13 @@ class Disp(nn.Module):
         refuse_autograd("Disp.forward_stats", x)
         return DispStats(*ops.disp_softargmin_stats(x, self.maxdisp, out, stats))
 
+    def forward_train_stats(self, x):
+        """forward_stats under autograd -> DispStats whose .disp and .tensor carry the graph (ag.DispStatsFn: the adjoint of the
+        disparity, variance, peak and entropy in one launch).  .disp is forward's result bit for bit.  fp32 only."""
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"Disp.forward_train_stats: fp32 only (got {x.dtype}): the statistics' adjoint is not built for bf16 costs")
+        return DispStats(*ag.DispStatsFn.apply(x, self.maxdisp))
+
 
 def _scale_dimension(dim, scale):
     """rag_model.py:140-141 (and build_model_3d.py's cell): the size of one axis after a x0.5 / x2 resample."""
@@ -1128,3 +1135,15 @@ class MatchingNet(nn.Module):
         with torch.no_grad():
             cost = self.matching(None, task_arch, None, features=(left_fea, right_fea))
             return self.disp.forward_stats(cost, out, stats)
+
+    def forward_train_stats(self, left_fea, right_fea, task_arch=None):
+        """forward under autograd with the head's statistics launch and its adjoint (Disp.forward_train_stats) -> DispStats whose
+        .disp and .tensor carry the graph.  fp32 only."""
+        if task_arch is None:
+            task_arch = self.arch_init
+        if left_fea.shape != right_fea.shape or left_fea.dim() != 4:
+            raise ValueError("MatchingNet: left/right features must both be [B, C, h, w]")
+        if left_fea.dtype != torch.float32 or right_fea.dtype != torch.float32:
+            raise RuntimeError(f"MatchingNet.forward_train_stats: fp32 only (got {left_fea.dtype}, {right_fea.dtype})")
+        cost = self.matching(None, task_arch, None, features=(left_fea, right_fea))
+        return self.disp.forward_train_stats(cost)

@@ -166,6 +166,15 @@ class Network(MatchingNet):
             cost = self.matching(None, task_arch, path, features=(lf, rf))
             return self.disp.forward_stats(cost, out, stats)
 
+    def forward_train_stats(self, left, right, t, task_arch=None, path=None):
+        """forward under autograd (two feature passes in training mode, as forward) with the head's statistics launch and its
+        adjoint in place of the plain pair -> DispStats whose .disp and .tensor carry the graph.  fp32 only."""
+        if left.dtype != torch.float32 or right.dtype != torch.float32:
+            raise RuntimeError(f"Network.forward_train_stats: fp32 only (got {left.dtype}, {right.dtype})")
+        lf, rf = self._features(left, right, lambda x: self.feature(x, task_arch, path))
+        cost = self.matching(None, task_arch, path, features=(lf, rf))
+        return self.disp.forward_train_stats(cost)
+
     def search_forward_stats(self, left, right, t, selected_ops, out=None, stats=None):
         """search_forward with the head's statistics launch -> DispStats; inference only."""
         refuse_autograd("Network.search_forward_stats", left, right)

@@ -1032,6 +1032,72 @@ def disp_softargmin_bwd(cost: torch.Tensor, dout: torch.Tensor, maxdisp: int) ->
     return dc.reshape(shape)
 
 
+def disp_softargmin_stats_bwd(cost: torch.Tensor, dout: Optional[torch.Tensor], dstats: Optional[torch.Tensor], maxdisp: int) -> torch.Tensor:
+    """adjoint of disp_softargmin_stats: dcost with cost's shape from dout [B,3h,3w] and dstats [B,3,3h,3w] (variance, peak, entropy);
+    either may be None (no cotangent: a NULL pointer, the bits of a zero tensor), not both.  fp32 only."""
+    _need_gpu(cost, dout, dstats)
+    if dout is None and dstats is None:
+        raise ValueError("disp_softargmin_stats_bwd: dout and dstats are both None")
+    shape = cost.shape
+    if cost.dim() == 5 and cost.shape[1] != 1:
+        raise ValueError("disp_softargmin_stats_bwd: expected a single-channel cost volume")
+    c4 = (cost[:, 0] if cost.dim() == 5 else cost).contiguous()
+    B, d, h, w = c4.shape
+    if dout is not None and tuple(dout.shape) != (B, 3 * h, 3 * w):
+        raise ValueError(f"disp_softargmin_stats_bwd: dout must be [{B}, {3 * h}, {3 * w}]")
+    if dstats is not None and tuple(dstats.shape) != (B, 3, 3 * h, 3 * w):
+        raise ValueError(f"disp_softargmin_stats_bwd: dstats must be [{B}, 3, {3 * h}, {3 * w}]")
+    dout = dout.contiguous() if dout is not None else None
+    dstats = dstats.contiguous() if dstats is not None else None
+    dc = torch.zeros_like(c4)
+    check(load_library().ragmi_disp_softargmin_stats_bwd(c4.data_ptr(), dout.data_ptr() if dout is not None else None,
+                                                         dstats.data_ptr() if dstats is not None else None, dc.data_ptr(), B, d, h, w,
+                                                         int(maxdisp), 3 * h, 3 * w, _stream()), "disp_softargmin_stats_bwd")
+    return dc.reshape(shape)
+
+
+def _loss_inputs(what: str, disp_est: torch.Tensor, stats: torch.Tensor, disp_gt: torch.Tensor):
+    _need_gpu(disp_est, stats, disp_gt)
+    if disp_est.dim() != 3 or disp_gt.shape != disp_est.shape or tuple(stats.shape) != (disp_est.shape[0], 3) + tuple(disp_est.shape[1:]):
+        raise ValueError(f"{what}: disp_est and disp_gt must both be [B, H, W] and stats [B, 3, H, W]")
+    return disp_est.contiguous(), stats.contiguous(), disp_gt.contiguous()
+
+
+def uncertainty_loss_fwd(disp_est: torch.Tensor, stats: torch.Tensor, disp_gt: torch.Tensor, maxdisp: float, var_floor: float = 1.0 / 12.0,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The uncertainty-aware loss launch (ragmi_uncertainty_loss_fwd) -> the 4-float device vector (loss, masked smooth-L1 mean, mean
+    sqrt(variance + var_floor) over the mask, masked pixel count).  `out`: a caller-owned contiguous 4-float tensor."""
+    est, st, gt = _loss_inputs("uncertainty_loss_fwd", disp_est, stats, disp_gt)
+    B, H, W = est.shape
+    lib = load_library()
+    if out is None:
+        out = torch.empty((4,), device=est.device, dtype=torch.float32)
+    _need_gpu(out)
+    if tuple(out.shape) != (4,) or not out.is_contiguous() or out.device != est.device:
+        raise ValueError("uncertainty_loss_fwd: out must be a contiguous 4-float tensor on the input's device")
+    acc = torch.empty((lib.ragmi_uncertainty_loss_workspace_elems(B, H, W),), device=est.device, dtype=torch.float32)
+    check(lib.ragmi_uncertainty_loss_fwd(est.data_ptr(), st.data_ptr(), gt.data_ptr(), B, H, W, float(maxdisp), float(var_floor),
+                                         acc.data_ptr(), out.data_ptr(), _stream()), "uncertainty_loss_fwd")
+    return out
+
+
+def uncertainty_loss_bwd(disp_est: torch.Tensor, stats: torch.Tensor, disp_gt: torch.Tensor, out: torch.Tensor, gout: torch.Tensor,
+                         maxdisp: float, var_floor: float = 1.0 / 12.0, ddisp: Optional[torch.Tensor] = None,
+                         dstats: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Gradient of uncertainty_loss_fwd's out[0] scaled by the 1-float device tensor gout, one launch -> (ddisp [B,H,W], dstats
+    [B,3,H,W] with zeros in the peak and entropy planes).  `ddisp` / `dstats`: caller-owned outputs (a captured graph's)."""
+    est, st, gt = _loss_inputs("uncertainty_loss_bwd", disp_est, stats, disp_gt)
+    B, H, W = est.shape
+    _need_gpu(out, gout)
+    if out.numel() != 4 or gout.numel() != 1 or not out.is_contiguous():
+        raise ValueError("uncertainty_loss_bwd: out must be the forward's 4 floats and gout one float")
+    ddisp, dstats = _stats_outputs("uncertainty_loss_bwd", est, B, H, W, ddisp, dstats)
+    check(load_library().ragmi_uncertainty_loss_bwd(est.data_ptr(), st.data_ptr(), gt.data_ptr(), out.data_ptr(), gout.data_ptr(),
+                                                    ddisp.data_ptr(), dstats.data_ptr(), B, H, W, float(maxdisp), float(var_floor),
+                                                    _stream()), "uncertainty_loss_bwd")
+    return ddisp, dstats
+
+
 def conv2d_k3_strided_dgrad(g: torch.Tensor, weight: torch.Tensor, in_hw: Sequence[int], stride: int) -> torch.Tensor:
     """data gradient of the strided 2-D stem conv: g[B,Cout,Ho,Wo] -> dx[B,Cin,H,W]."""
     _need_gpu(g, weight)

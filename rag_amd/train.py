@@ -94,6 +94,32 @@ def self_supervised_loss(disp: torch.Tensor, left: torch.Tensor, right: torch.Te
     return re_and_sm_loss_torch(disp, left, right)[0]
 
 
+def uncertainty_loss(disp: torch.Tensor, stats: torch.Tensor, gt: torch.Tensor, maxdisp: int, var_floor: float = 1.0 / 12.0) -> torch.Tensor:
+    """The uncertainty-aware loss of rag_amd.metrics over the head's own variance (disp, stats of a forward_train_stats call): the
+    fused HIP loss on the GPU, its plain-torch twin on CPU tensors."""
+    from .metrics import uncertainty_loss as fused
+    return fused(disp, stats, gt, maxdisp, var_floor)
+
+
+def _check_uncertainty(uncertainty: bool, net, supervise: bool, sampled_ops, selected_ops, meter) -> None:
+    """Argument checks of uncertainty=True, before any launch."""
+    if not uncertainty:
+        return
+    if not supervise:
+        raise ValueError("uncertainty=True trains on the ground truth: supervise=False is refused")
+    if sampled_ops is not None:
+        raise ValueError("uncertainty=True is built for the grown stereo Network and a MatchingNet on features: sampled_ops (the cell "
+                         "search's supernet) is refused")
+    if selected_ops is not None:
+        raise ValueError("uncertainty=True is built for the grown stereo Network and a MatchingNet on features: selected_ops (the unit "
+                         "search) is refused")
+    if _is_depth(net) or _supernet_kind(net) is not None:
+        raise ValueError("uncertainty=True needs the stereo head's distribution: a depth network or a supernet is refused")
+    if meter is not None:
+        raise ValueError("uncertainty=True: an EpochMeter is fed by the masked smooth-L1 launch, which this step does not run: meter is "
+                         "refused")
+
+
 def _is_depth(net) -> bool:
     from .depth import Network as DepthNetwork
     return isinstance(net, DepthNetwork)
@@ -170,7 +196,8 @@ TRAIN_PRECISION = "fp32"     # the reference's training step is fp32 (rag.py:204
 
 def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None, features: bool = False,
                      precision: Optional[str] = None, supervise: bool = True, sampled_ops: Optional[Sequence] = None,
-                     selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None):
+                     selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None, uncertainty: bool = False,
+                     var_floor: float = 1.0 / 12.0):
     """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  A depth network (rag_amd.depth.Network):
     Network.forward_train(left) -> silog_loss(depth, gt) with gt the ground-truth depth in metres (0 = invalid) as in
     rag_depth/src/approaches/rag.py:232-242; `right` may be None.  `supervise=False`: the self-supervised loss
@@ -186,8 +213,12 @@ def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None
     (rag.py:371-382): forward net.search_forward(left, right, t, selected_ops), masked smooth-L1 against net.maxdisp; the module
     modes are the caller's (net.search_mode()); sampled_ops, task_arch, features=True, supervise=False, another kind of net, a
     missing t or gt, a wrong length and an index outside its list are refused.  `meter` (rag_amd.metrics.EpochMeter): the masked
-    smooth-L1 launch also adds this batch to the epoch's meter (rag.py:386-396 scores the disp_est it trained on).  Returns the
-    (detached) loss."""
+    smooth-L1 launch also adds this batch to the epoch's meter (rag.py:386-396 scores the disp_est it trained on).
+    `uncertainty=True` (the grown stereo Network, or a MatchingNet with features=True; supervised): forward_train_stats in place of
+    forward and rag_amd.metrics.uncertainty_loss(disp, stats, gt, net.maxdisp, var_floor) in place of the masked smooth-L1, so the
+    variance the head reports is trained; supervise=False, sampled_ops, selected_ops, a depth network and a meter are refused.
+    Returns the (detached) loss."""
+    _check_uncertainty(uncertainty, net, supervise, sampled_ops, selected_ops, meter)
     sel = _check_selected(net, selected_ops, t, gt, sampled_ops, task_arch, features, supervise)
     kind = _check_sampled(net, sampled_ops, gt, task_arch, features, supervise)
     depth = _is_depth(net)
@@ -208,6 +239,10 @@ def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None
         elif depth:
             from .depth import silog_loss
             loss = silog_loss(net.forward_train(left, 0, task_arch if task_arch is not None else net.arch_init), gt)
+        elif uncertainty:
+            res = net.forward_train_stats(left, right, task_arch) if features else \
+                net.forward_train_stats(left, right, 0, task_arch if task_arch is not None else net.arch_init)
+            loss = uncertainty_loss(res.disp, res.tensor, gt, net.maxdisp, var_floor)
         else:
             disp = net(left, right, task_arch) if features else net(left, right, 0, task_arch if task_arch is not None else net.arch_init)
             loss = masked_smooth_l1(disp, gt, net.maxdisp, meter) if supervise else self_supervised_loss(disp, left, right)
@@ -342,13 +377,15 @@ def search_eval_step(net, left, right, gt, t, selected_ops, meter=None):
 
 def train_step(net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                features: bool = False, precision: Optional[str] = None, supervise: bool = True,
-               sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None):
-    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision`, `supervise`, `sampled_ops`, `selected_ops` / `t`
-    and `meter` as in forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops` the optimizer updates
-    net.active_parameters(*sampled_ops) only (exchange_and_update), with `selected_ops` (one batch of Appr.search_epoch,
-    rag.py:371-396) net.active_parameters(t, selected_ops).  Returns the (detached) loss."""
+               sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None,
+               uncertainty: bool = False, var_floor: float = 1.0 / 12.0):
+    """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision`, `supervise`, `sampled_ops`, `selected_ops` / `t`,
+    `meter` and `uncertainty` / `var_floor` as in forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops`
+    the optimizer updates net.active_parameters(*sampled_ops) only (exchange_and_update), with `selected_ops` (one batch of
+    Appr.search_epoch, rag.py:371-396) net.active_parameters(t, selected_ops).  Returns the (detached) loss."""
     loss = forward_backward(net, bucket, left, right, gt, task_arch=task_arch, features=features, precision=precision,
-                            supervise=supervise, sampled_ops=sampled_ops, selected_ops=selected_ops, t=t, meter=meter)
+                            supervise=supervise, sampled_ops=sampled_ops, selected_ops=selected_ops, t=t, meter=meter,
+                            uncertainty=uncertainty, var_floor=var_floor)
     active = _active_of(net, sampled_ops, selected_ops, t)
     exchange_and_update(optimizer, bucket, clip=clip, dist=dist, active=active)
     return loss
@@ -437,11 +474,16 @@ class GraphedTrainStep(_GraphedStep):
 
     `selected_ops=, t=, meter=`: the unit search's step (forward_backward), one object per epoch in the same way (a path holds for an
     epoch, rag.py:275-290).  The meter's update is part of the captured loss launch: every replay adds its batch to `meter.sums`, and
-    `meter.last` stays the static vector the replays rewrite."""
+    `meter.last` stays the static vector the replays rewrite.
+
+    `uncertainty=True, var_floor=`: the uncertainty-aware step of forward_backward; the statistics launch, the loss and both adjoints are
+    kernels, so the census holds as for the plain step."""
 
     def __init__(self, net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                  features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True,
-                 sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None):
+                 sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None,
+                 uncertainty: bool = False, var_floor: float = 1.0 / 12.0):
+        _check_uncertainty(uncertainty, net, supervise, sampled_ops, selected_ops, meter)
         sel = _check_selected(net, selected_ops, t, gt, sampled_ops, task_arch, features, supervise)
         if _check_sampled(net, sampled_ops, gt, task_arch, features, supervise) is None and sel is None:
             _check_supervision(gt, features, supervise, _is_depth(net))
@@ -453,7 +495,7 @@ class GraphedTrainStep(_GraphedStep):
         self.gt = gt.clone() if gt is not None else None
         self.precision = precision or TRAIN_PRECISION
         kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise, sampled_ops=sampled_ops,
-                  selected_ops=sel, t=t, meter=meter)
+                  selected_ops=sel, t=t, meter=meter, uncertainty=uncertainty, var_floor=var_floor)
         self._capture(lambda: forward_backward(net, bucket, self.left, self.right, self.gt, **kw), warmup)
 
     def __call__(self, left=None, right=None, gt=None):
