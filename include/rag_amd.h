@@ -428,6 +428,35 @@ int ragmi_disp_softargmin_stats_fwd(const void* cost, void* out, void* stats, in
 int ragmi_disparity_regression_stats_fwd(const void* prob, void* out, void* stats, int B, int D, int H, int W,
                                          int dtype, void* stream);
 
+/*
+ * The head with a mode-local disparity, in the same pass (rag_model.py:18-44 keeps only the mean; at a depth edge the
+ * distribution has two wells and the mean lies on neither surface).  With p_k as above and an integer radius,
+ * 0 <= radius <= maxdisp, in fine-disparity pixels, per output pixel:
+ *   index = k*, the fine index of the smallest upsampled cost as the kernel's fp32 arithmetic produces it; the lowest
+ *           index on exactly equal values.  In the tiled kernels k* = 3 am + 1 with am the first minimum over the coarse
+ *           plane samples (fine sample 3 am + 1 sits on that plane), and k* = 0 when am = 0 (fine samples 0 and 1 are
+ *           both plane 0: the source index is clamped).  Stored as an integer-valued fp32.
+ *   W     = {k : |k - k*| <= radius, 0 <= k < maxdisp}          clipped at both ends, not renormalised to a full width
+ *   mass  = sum_W p_k
+ *   disp  = k* + sum_W p_k (k - k*) / mass                      the sum about k*, as the variance runs about its pivot
+ * radius = 0 gives disp = k* exactly; radius = maxdisp gives disp = out and mass = 1 up to rounding.
+ * out: [B, Ho, Wo] and stats: [B, 3, Ho, Wo] are the SAME BITS as ragmi_disp_softargmin_stats_fwd on the same input.
+ * mode: [B, 3, Ho, Wo] fp32, planes (index, disp, mass).  One launch; arguments, refusals, status codes and the choice
+ * between the tiled and the generic kernel are those of ragmi_disp_softargmin_stats_fwd; a null mode, radius < 0 and
+ * radius > maxdisp are RAGMI_EINVAL before any launch.  radius is a kernel argument: no rebuild, no second code path.
+ */
+int ragmi_disp_softargmin_mode_fwd(const void* cost, void* out, void* stats, void* mode, int B, int d, int h, int w,
+                                   int maxdisp, int Ho, int Wo, int radius, int dtype, void* stream);
+
+/*
+ * DisparityRegression.forward (rag_model.py:18-29) with the statistics and the mode-local disparity of prob[B, D, H, W],
+ * taken as given: k* is the FIRST arg-max of prob, the sums run over prob itself, and a window without mass gives
+ * disp = k*.  out and stats are the bits of ragmi_disparity_regression_stats_fwd; mode [B, 3, H, W] = (index, disp,
+ * mass).  A one-hot prob gives (its index, its index, 1) exactly.  0 <= radius <= D, else RAGMI_EINVAL.
+ */
+int ragmi_disparity_regression_mode_fwd(const void* prob, void* out, void* stats, void* mode, int B, int D, int H, int W,
+                                        int radius, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Cost volume + stem3d0 in one step, without materialising the cost volume (rag_model.py:375-383 followed by
  * ConvBR_3d(2C, Cout, 3, 1, 1), rag_model.py:234/341).  The left half of the cost volume does not depend on the disparity

@@ -173,6 +173,10 @@ SIGNATURES = {
     "ragmi_disp_softargmin_stats_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                 c_int, c_void_p]),
     "ragmi_disparity_regression_stats_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ragmi_disp_softargmin_mode_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_int, c_int, c_void_p]),
+    "ragmi_disparity_regression_mode_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                    c_void_p]),
     "ragmi_disp_softargmin_stats_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                                 c_void_p]),
     "ragmi_uncertainty_loss_workspace_elems": (c_int64, [c_int, c_int, c_int]),

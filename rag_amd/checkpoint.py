@@ -21,6 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .metrics import MODE_RADIUS
 from .modules import _ConvBR, Genotype
 from .network import Network
 
@@ -154,3 +155,9 @@ class MultiTaskStereo(nn.Module):
         if not 0 <= t < len(self.archis):
             raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
         return self.net.forward_stats(left, right, t, self.archis[t], out=out, stats=stats)
+
+    def forward_mode(self, left, right, t: int, radius=MODE_RADIUS, out=None, stats=None, mode=None):
+        """forward with the mode-local disparity and its window's mass (Network.forward_mode) -> DispMode; inference only."""
+        if not 0 <= t < len(self.archis):
+            raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
+        return self.net.forward_mode(left, right, t, self.archis[t], radius=radius, out=out, stats=stats, mode=mode)

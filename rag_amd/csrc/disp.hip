@@ -55,8 +55,38 @@ struct DispMoments {
   }
 };
 
-template <class T, bool STATS>
-__device__ __forceinline__ void disp_softargmin_body(const DispArgs& a, float* stats) {
+// Mode-local regression (the MODE = true instantiations; they are STATS instantiations too).  k* is the fine index of the smallest
+// upsampled cost (the lowest one on exact ties), W = {k : |k - k*| <= radius} clipped to [0, maxdisp) and not renormalised to a full
+// width.  With the weights e_k the kernels already hold:
+//   mode_mass = sum_W e_k / s,   mode_disp = k* + sum_W e_k (k - k*) / sum_W e_k       (about k*, as the moments run about their pivot)
+// At a depth edge the softmin has two wells and out = sum p_k k lies between the two surfaces; mode_disp stays on the stronger one
+// and mode_mass says how much of the distribution it speaks for.  mode: [B, 3, Ho, Wo] fp32, planes (index, disp, mass).
+// Per fine sample: a subtract, a compare, a select and two accumulations.  The d = 64 register form then needs 103 VGPRs (the STATS one
+// 95): no scratch, 4 waves per SIMD instead of 5; 42.7 -> 54.6 us at 384 x 1248.
+struct DispWindow {
+  float ks = 0.f, rf = 0.f, w0 = 0.f, w1 = 0.f;
+  float c0[3] = {0.f, 0.f, 0.f}, c1[3] = {0.f, 0.f, 0.f};       // the chains and flush() cadence of DispMoments
+  __device__ __forceinline__ void add_chain(int j, float e, float fd) {
+    const float t = fd - ks, ew = fabsf(t) <= rf ? e : 0.f;
+    c0[j] += ew;
+    c1[j] = fmaf(ew, t, c1[j]);
+  }
+  __device__ __forceinline__ void flush() {
+    w0 += (c0[0] + c0[1]) + c0[2];
+    w1 += (c1[0] + c1[1]) + c1[2];
+    c0[0] = c0[1] = c0[2] = c1[0] = c1[1] = c1[2] = 0.f;
+  }
+  __device__ __forceinline__ void store(float* mode, int64_t b, int64_t npix, int64_t o, float s) const {
+    float* const p = mode + b * 3 * npix + o;
+    p[0] = ks;
+    p[npix] = w0 > 0.f ? ks + w1 / w0 : ks;
+    p[2 * npix] = w0 / s;
+  }
+};
+
+template <class T, bool STATS, bool MODE = false>
+__device__ __forceinline__ void disp_softargmin_body(const DispArgs& a, float* stats, float* mode = nullptr, int radius = 0) {
+  static_assert(STATS || !MODE, "the mode instantiations write the statistics too");
   extern __shared__ float4 ztab[];                 // [maxdisp]
   for (int dd = threadIdx.x; dd < a.maxdisp; dd += 256) {
     const LinIdx lz = lin_index(dd, a.d, a.maxdisp, a.sd, 0);
@@ -138,12 +168,42 @@ __device__ __forceinline__ void disp_softargmin_body(const DispArgs& a, float* s
     mo.flush();
     mo.store(stats, b, npix, o, s);
   }
+  if constexpr (MODE) {
+    // k* is where the running maximum last moved (t > m is strict: the lowest index of equal costs), known only now: a second walk
+    // over the at most 2 radius + 1 fine samples around it, with the taps, the plane clamping and the lerp of the walk above; the
+    // weights are taken against the final maximum m.  One chain in blocks of 16 samples, as above.
+    DispWindow wd;
+    wd.ks = mo.pv;
+    wd.rf = (float)radius;
+    const int ks = (int)mo.pv, d_lo = max(ks - radius, 0), d_hi = min(ks + radius, a.maxdisp - 1);
+    cz = (int)ztab[d_lo].x;
+    b0 = plane(cz);
+    b1 = plane(cz + 1 < a.d ? cz + 1 : a.d - 1);
+    for (int dd = d_lo; dd <= d_hi; ++dd) {
+      const float4 tb = ztab[dd];
+      const int i0 = (int)tb.x;
+      while (i0 > cz) {
+        ++cz;
+        b0 = b1;
+        b1 = plane(cz + 1 < a.d ? cz + 1 : a.d - 1);
+      }
+      const float t = -fmaf(tb.y + tb.w, b0, tb.z * b1);
+      wd.add_chain(0, __builtin_amdgcn_exp2f((t - m) * K), (float)dd);
+      if (((dd - d_lo) & 15) == 15) wd.flush();
+    }
+    wd.flush();
+    wd.store(mode, b, npix, o, s);
+  }
 }
 
 template <class T>
 __global__ __launch_bounds__(256) void disp_softargmin_kernel(DispArgs a) { disp_softargmin_body<T, false>(a, nullptr); }
 template <class T>
 __global__ __launch_bounds__(256) void disp_softargmin_stats_kernel(DispArgs a, float* stats) { disp_softargmin_body<T, true>(a, stats); }
+template <class T>
+__global__ __launch_bounds__(256) void disp_softargmin_mode_kernel(DispArgs a, float* stats, float* mode, int radius) {
+  disp_softargmin_body<T, true, true>(a, stats, mode, radius);
+}
 
 // The reference's own shape — maxdisp = 3 d and a 3x spatial upsampling (rag_model.py:40, 272-273) — as a tiled, two-pass kernel.
 //  * A workgroup owns 8 x 32 output pixels; the coarse cost block they interpolate from (d planes x 5 x 13 values) is staged through
@@ -160,8 +220,9 @@ __global__ __launch_bounds__(256) void disp_softargmin_stats_kernel(DispArgs a, 
 //    fmaf(w0, b0, w1 * b1).
 constexpr int DX3_TY = 8, DX3_TX = 32, DX3_CR = 5, DX3_CC = 13, DX3_CP = DX3_CR * DX3_CC;
 
-template <class T, bool STATS>
-__device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float* stats) {
+template <class T, bool STATS, bool MODE = false>
+__device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float* stats, float* mode = nullptr, int radius = 0) {
+  static_assert(STATS || !MODE, "the mode instantiations write the statistics too");
   extern __shared__ __attribute__((aligned(16))) float dx3_lds[];
   float4* const ztab = reinterpret_cast<float4*>(dx3_lds);            // [maxdisp] (wp, wc, wn, dd)
   float* const tile = dx3_lds + 4 * a.maxdisp;                        // [d][5][13]
@@ -211,6 +272,10 @@ __device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float
   // plane); the softmin's mode is within a coarse step of it
   DispMoments mo;
   int am = 0;
+  // MODE: fine sample 3 am + 1 sits exactly on plane am, the smallest of the planes every fine sample is a convex combination of, so
+  // k* = 3 am + 1 - except am == 0: the source index is clamped at 0, fine samples 0 and 1 both evaluate to v[0], and k* = 0
+  DispWindow wd;
+  wd.rf = (float)radius;
   // d = 64 (maxdisp 192, the reference's only configuration, rag_model.py:274): the 64 plane samples of pass 1 stay in REGISTERS for
   // pass 2 — no second round of 4 d LDS reads and bilinear arithmetic (same operations on the same values: identical bits).  Chunks
   // of 8 planes fenced by sched_barrier: unfenced, the scheduler hoisted all 256 operand reads and the kernel spilled or ran at
@@ -228,6 +293,7 @@ __device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float
 #pragma unroll
       for (int z = 63; z >= 0; --z) am = v[z] == lo ? z : am;
       mo.pv = (float)(3 * am + 1);
+      if constexpr (MODE) wd.ks = am == 0 ? 0.f : mo.pv;
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -242,9 +308,11 @@ __device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float
         s += e;
         ws = fmaf(e, tb.w, ws);
         if constexpr (STATS) mo.add_chain(j, e, x, tb.w);
+        if constexpr (MODE) wd.add_chain(j, e, tb.w);
       }
       if ((k & 7) == 7) {
         if constexpr (STATS) mo.flush();
+        if constexpr (MODE) wd.flush();
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -257,6 +325,7 @@ __device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float
     lo = fminf(lo, vz);
   }
   if constexpr (STATS) mo.pv = (float)(3 * am + 1);
+  if constexpr (MODE) wd.ks = am == 0 ? 0.f : mo.pv;
   // exponent of a sample: (min - cost) * K: the difference is formed BEFORE the scaling by K, like the generic kernel, so large
   // |cost| does not lose the bits that matter near the minimum
   float vc = plane(0), vp = vc, vn = plane(min(1, D - 1));
@@ -270,15 +339,19 @@ __device__ __forceinline__ void disp_softargmin_x3_body(const DispArgs& a, float
       s += e;
       ws = fmaf(e, tb.w, ws);
       if constexpr (STATS) mo.add_chain(j, e, x, tb.w);
+      if constexpr (MODE) wd.add_chain(j, e, tb.w);
     }
     vp = vc; vc = vn; vn = plane(min(k + 2, D - 1));
     if constexpr (STATS) if ((k & 7) == 7) mo.flush();
+    if constexpr (MODE) if ((k & 7) == 7) wd.flush();
   }
   if constexpr (STATS) mo.flush();
+  if constexpr (MODE) wd.flush();
   }
   if (ox0 + tx < a.Wo && oy0 + ty < a.Ho) {
     a.out[(int64_t)b * a.Ho * a.Wo + (int64_t)oy * a.Wo + ox] = ws / s;
     if constexpr (STATS) mo.store(stats, b, (int64_t)a.Ho * a.Wo, (int64_t)oy * a.Wo + ox, s);
+    if constexpr (MODE) wd.store(mode, b, (int64_t)a.Ho * a.Wo, (int64_t)oy * a.Wo + ox, s);
   }
 }
 
@@ -286,6 +359,10 @@ template <class T>
 __global__ __launch_bounds__(256) void disp_softargmin_x3_kernel(DispArgs a) { disp_softargmin_x3_body<T, false>(a, nullptr); }
 template <class T>
 __global__ __launch_bounds__(256) void disp_softargmin_x3_stats_kernel(DispArgs a, float* stats) { disp_softargmin_x3_body<T, true>(a, stats); }
+template <class T>
+__global__ __launch_bounds__(256) void disp_softargmin_x3_mode_kernel(DispArgs a, float* stats, float* mode, int radius) {
+  disp_softargmin_x3_body<T, true, true>(a, stats, mode, radius);
+}
 
 // The wavefront-reduction form north_star names, for the same configuration (maxdisp = 3 d, 3x upsampling): 16 lanes share one
 // output pixel, lane l owns the coarse planes 4l .. 4l+3 (d <= 64) and their 12 fine samples; a wave step is 4 pixels.
@@ -401,9 +478,12 @@ __global__ __launch_bounds__(256) void disparity_regression_kernel(const T* __re
 // bits), variance = sum p (k - out)^2 by the definition in a second walk over the D planes (a one-hot prob gives exactly 0: out is
 // exactly its index), peak = max p, entropy = -sum_{p > 0} p ln p.  The two stat sums run in 8 interleaved partial sums: there is no
 // interpolation error to hide behind here, and a serial fp32 sum of 192 terms alone is ~5e-7 of the result.
-template <class T>
-__global__ __launch_bounds__(256) void disparity_regression_stats_kernel(const T* __restrict__ prob, float* __restrict__ out,
-                                                                        float* __restrict__ stats, int D, int64_t hw) {
+// MODE: k* is the first arg-max of prob (found in the statistics walk: strictly greater moves it), and a third walk over the window
+// |k - k*| <= radius alone sums prob and prob (k - k*), in 8 interleaved partial sums again: mode = (k*, k* + sum p (k - k*) / sum p,
+// sum p), and a window without mass gives mode_disp = k*.  A one-hot prob gives (its index, its index, 1) exactly.
+template <class T, bool MODE>
+__device__ __forceinline__ void disparity_regression_stats_body(const T* __restrict__ prob, float* __restrict__ out, float* __restrict__ stats,
+                                                                int D, int64_t hw, float* __restrict__ mode = nullptr, int radius = 0) {
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (o >= hw) return;
   const int b = blockIdx.y;
@@ -412,6 +492,8 @@ __global__ __launch_bounds__(256) void disparity_regression_stats_kernel(const T
 #pragma unroll 8
   for (int dd = 0; dd < D; ++dd) acc = fmaf(ld(p + (int64_t)dd * hw), (float)dd, acc);
   float var[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ent[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pk = 0.f;
+  float best = -INFINITY;
+  int ks = 0;
   for (int d0 = 0; d0 < D; d0 += 8) {
     static_for<8>([&](auto J) {
       constexpr int j = decltype(J)::value;
@@ -420,6 +502,12 @@ __global__ __launch_bounds__(256) void disparity_regression_stats_kernel(const T
         var[j] = fmaf(q * t, t, var[j]);
         ent[j] = q > 0.f ? fmaf(q, logf(q), ent[j]) : ent[j];
         pk = fmaxf(pk, q);
+        if constexpr (MODE) {
+          if (q > best) {
+            best = q;
+            ks = d0 + j;
+          }
+        }
       }
     });
   }
@@ -428,6 +516,38 @@ __global__ __launch_bounds__(256) void disparity_regression_stats_kernel(const T
   st[0] = ((var[0] + var[1]) + (var[2] + var[3])) + ((var[4] + var[5]) + (var[6] + var[7]));
   st[hw] = pk;
   st[2 * hw] = 0.f - (((ent[0] + ent[1]) + (ent[2] + ent[3])) + ((ent[4] + ent[5]) + (ent[6] + ent[7])));
+  if constexpr (MODE) {
+    float w0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, w1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int d_lo = max(ks - radius, 0), d_hi = min(ks + radius, D - 1);
+    for (int d0 = d_lo; d0 <= d_hi; d0 += 8) {
+      static_for<8>([&](auto J) {
+        constexpr int j = decltype(J)::value;
+        if (d0 + j <= d_hi) {
+          const float q = ld(p + (int64_t)(d0 + j) * hw);
+          w0[j] += q;
+          w1[j] = fmaf(q, (float)(d0 + j - ks), w1[j]);
+        }
+      });
+    }
+    const float m0 = ((w0[0] + w0[1]) + (w0[2] + w0[3])) + ((w0[4] + w0[5]) + (w0[6] + w0[7]));
+    const float m1 = ((w1[0] + w1[1]) + (w1[2] + w1[3])) + ((w1[4] + w1[5]) + (w1[6] + w1[7]));
+    float* const mp = mode + (int64_t)b * 3 * hw + o;
+    mp[0] = (float)ks;
+    mp[hw] = m0 != 0.f ? (float)ks + m1 / m0 : (float)ks;
+    mp[2 * hw] = m0;
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void disparity_regression_stats_kernel(const T* __restrict__ prob, float* __restrict__ out,
+                                                                        float* __restrict__ stats, int D, int64_t hw) {
+  disparity_regression_stats_body<T, false>(prob, out, stats, D, hw);
+}
+template <class T>
+__global__ __launch_bounds__(256) void disparity_regression_mode_kernel(const T* __restrict__ prob, float* __restrict__ out,
+                                                                       float* __restrict__ stats, float* __restrict__ mode, int D, int64_t hw,
+                                                                       int radius) {
+  disparity_regression_stats_body<T, true>(prob, out, stats, D, hw, mode, radius);
 }
 
 }  // namespace ragmi
@@ -525,4 +645,54 @@ extern "C" int ragmi_disparity_regression_stats_fwd(const void* prob, void* out,
   else
     hipLaunchKernelGGL(disparity_regression_stats_kernel<float>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), (const float*)prob, (float*)out, (float*)stats, D, hw);
   return check_launch("disparity_regression_stats");
+}
+
+// The mode launches: the argument checks, the dispatch rule and the launch geometry of the statistics entry points above, one launch
+// each; radius is a run-time argument of the kernels.
+extern "C" int ragmi_disp_softargmin_mode_fwd(const void* cost, void* out, void* stats, void* mode, int B, int d, int h, int w,
+                                              int maxdisp, int Ho, int Wo, int radius, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(cost && out && stats && mode, RAGMI_EINVAL, "disp_softargmin_mode: null pointer");
+  RAGMI_REQUIRE(B > 0 && d > 0 && h > 0 && w > 0 && maxdisp > 0 && Ho > 0 && Wo > 0, RAGMI_EINVAL,
+                "disp_softargmin_mode: non-positive size");
+  RAGMI_REQUIRE(radius >= 0 && radius <= maxdisp, RAGMI_EINVAL, "disp_softargmin_mode: radius %d not in [0, maxdisp = %d]", radius, maxdisp);
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "disp_softargmin_mode: dtype %d not built", dtype);
+  RAGMI_REQUIRE(B <= 65535 && (int64_t)h * w < (1ll << 30), RAGMI_EUNSUPPORTED, "disp_softargmin_mode: size too large");
+  DispArgs a{cost, (float*)out, d, h, w, maxdisp, Ho, Wo,
+             lin_scale(d, maxdisp, 0), lin_scale(h, Ho, 0), lin_scale(w, Wo, 0)};
+  float* const st = (float*)stats;
+  float* const md = (float*)mode;
+  const hipStream_t q = static_cast<hipStream_t>(stream);
+  dim3 grid((unsigned)ceil_div((int64_t)Ho * Wo, 256), B);
+  const size_t lds = (size_t)maxdisp * sizeof(float4);
+  RAGMI_REQUIRE(lds <= 64 * 1024, RAGMI_EUNSUPPORTED, "disp_softargmin_mode: maxdisp %d exceeds the tap table (4096)", maxdisp);
+  const size_t lds3 = lds + (size_t)d * DX3_CP * sizeof(float);
+  if (maxdisp == 3 * d && Ho == 3 * h && Wo == 3 * w && lds3 <= 64 * 1024) {   // the tiled form (register form at d = 64, else the rolling window)
+    const dim3 g3((unsigned)ceil_div(Wo, DX3_TX), (unsigned)ceil_div(Ho, DX3_TY), (unsigned)B);
+    const dim3 g1((unsigned)(ceil_div((int64_t)g3.x * g3.y, 8) * 8), 1, (unsigned)B);
+    if (dtype == RAGMI_BF16) hipLaunchKernelGGL(disp_softargmin_x3_mode_kernel<bf16_t>, g1, dim3(256), lds3, q, a, st, md, radius);
+    else hipLaunchKernelGGL(disp_softargmin_x3_mode_kernel<float>, g1, dim3(256), lds3, q, a, st, md, radius);
+    return check_launch("disp_softargmin_mode");
+  }
+  if (dtype == RAGMI_BF16) hipLaunchKernelGGL(disp_softargmin_mode_kernel<bf16_t>, grid, dim3(256), lds, q, a, st, md, radius);
+  else hipLaunchKernelGGL(disp_softargmin_mode_kernel<float>, grid, dim3(256), lds, q, a, st, md, radius);
+  return check_launch("disp_softargmin_mode");
+}
+
+extern "C" int ragmi_disparity_regression_mode_fwd(const void* prob, void* out, void* stats, void* mode, int B, int D, int H, int W,
+                                                   int radius, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(prob && out && stats && mode, RAGMI_EINVAL, "disparity_regression_mode: null pointer");
+  RAGMI_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, RAGMI_EINVAL, "disparity_regression_mode: non-positive size");
+  RAGMI_REQUIRE(radius >= 0 && radius <= D, RAGMI_EINVAL, "disparity_regression_mode: radius %d not in [0, D = %d]", radius, D);
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "disparity_regression_mode: dtype %d not built", dtype);
+  RAGMI_REQUIRE(B <= 65535, RAGMI_EUNSUPPORTED, "disparity_regression_mode: B too large");
+  const int64_t hw = (int64_t)H * W;
+  dim3 grid((unsigned)ceil_div(hw, 256), B);
+  const hipStream_t q = static_cast<hipStream_t>(stream);
+  if (dtype == RAGMI_BF16)
+    hipLaunchKernelGGL(disparity_regression_mode_kernel<bf16_t>, grid, dim3(256), 0, q, (const bf16_t*)prob, (float*)out, (float*)stats, (float*)mode, D, hw, radius);
+  else
+    hipLaunchKernelGGL(disparity_regression_mode_kernel<float>, grid, dim3(256), 0, q, (const float*)prob, (float*)out, (float*)stats, (float*)mode, D, hw, radius);
+  return check_launch("disparity_regression_mode");
 }

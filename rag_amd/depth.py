@@ -364,6 +364,13 @@ class Network(_StereoNetwork):
                                   "the depth head has no distribution")
 
     search_forward_stats = forward_stats
+
+    def forward_mode(self, *args, **kwargs):
+        """The stereo head's mode-local disparity does not exist here, for the reason forward_stats gives."""
+        raise NotImplementedError("rag_amd.depth.Network: forward_mode belongs to the stereo head (a softmin over disparities); "
+                                  "the depth head has no distribution")
+
+    search_forward_mode = forward_mode
     forward_train_stats = forward_stats
 
     def search_forward_train(self, left, t, selected_ops):         # rag_model.py:716-740 under autograd (approaches/rag.py:405)

@@ -145,6 +145,87 @@ def disp_stats_torch(cost: torch.Tensor, maxdisp: int, size=None):
     return prob_stats_torch(F.softmin(v, dim=1))
 
 
+# --------------------------------------------------------------------------- mode-local disparity and the mass of its window
+MODE_NAMES = ("index", "disp", "mass")
+# The default window radius of forward_mode, in fine-disparity pixels: one coarse plane of the x3 head (3 fine px) plus one, so the window
+# always holds the mode's own coarse cell and a sample beyond it on each side.  A parameter like VAR_FLOOR, not a measurement.
+MODE_RADIUS = 4
+
+
+class DispMode(DispStats):
+    """Result of a `forward_mode` call: a DispStats (`.disp`, `.tensor` and its views: the bits of `forward_stats`) plus `.mode_tensor`
+    [B,3,H,W] with the views `.mode_index` (k*, the fine index of the smallest upsampled cost, integer-valued fp32), `.mode_disp` (the
+    disparity regressed over |k - k*| <= `.radius` about k*: it stays on one surface where `.disp` averages two) and `.mode_mass` (the
+    probability that window holds).  Everything stays on the device."""
+
+    def __init__(self, disp: torch.Tensor, tensor: torch.Tensor, mode_tensor: torch.Tensor, radius: int):
+        super().__init__(disp, tensor)
+        self.mode_tensor = mode_tensor
+        self.radius = int(radius)
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        if name in MODE_NAMES:
+            return self.mode_tensor[:, MODE_NAMES.index(name)]
+        return super().__getitem__(name)
+
+    @property
+    def mode_index(self) -> torch.Tensor:
+        return self.mode_tensor[:, 0]
+
+    @property
+    def mode_disp(self) -> torch.Tensor:
+        return self.mode_tensor[:, 1]
+
+    @property
+    def mode_mass(self) -> torch.Tensor:
+        return self.mode_tensor[:, 2]
+
+
+def _window_torch(p: torch.Tensor, radius: int, index: torch.Tensor) -> torch.Tensor:
+    """mode [B,3,H,W] = (k*, k* + sum_W p (k - k*) / sum_W p, sum_W p) of p[B,D,H,W] over W = {k : |k - k*| <= radius} about index = k*
+    [B,H,W]; the window is clipped at both ends and a window without mass gives k*."""
+    if int(radius) != radius or not 0 <= int(radius) <= p.shape[1]:
+        raise ValueError(f"rag_amd mode twin: radius must be an integer in [0, {p.shape[1]}], got {radius!r}")
+    ks = index.to(device=p.device, dtype=p.dtype)[:, None]
+    t = torch.arange(p.shape[1], dtype=p.dtype, device=p.device).view(1, -1, 1, 1) - ks
+    pw = p * (t.abs() <= int(radius))
+    mass = pw.sum(1)
+    m1 = (pw * t).sum(1)
+    safe = torch.where(mass != 0, mass, torch.ones_like(mass))
+    return torch.stack((ks[:, 0], ks[:, 0] + torch.where(mass != 0, m1 / safe, torch.zeros_like(m1)), mass), dim=1)
+
+
+def _first_index(x: torch.Tensor, extreme: torch.Tensor) -> torch.Tensor:
+    """The lowest index along dim 1 at which x equals its extreme [B,1,H,W], formed explicitly (argmax's tie order is not a contract)."""
+    idx = torch.arange(x.shape[1], device=x.device).view(1, -1, 1, 1)
+    return torch.where(x == extreme, idx, torch.full_like(idx, x.shape[1])).amin(1)
+
+
+def prob_mode_torch(prob: torch.Tensor, radius: int, index=None):
+    """(disp, stats, mode) of a distribution prob[B,D,H,W] taken as given, in prob's dtype and on its device: prob_stats_torch plus
+    mode [B,3,H,W] = (k*, mode_disp, mode_mass) with k* the FIRST arg-max of prob, or `index` [B,H,W] where it is given (the window
+    about a k* found elsewhere)."""
+    disp, stats = prob_stats_torch(prob)
+    if index is None:
+        index = _first_index(prob, prob.amax(1, keepdim=True))
+    return disp, stats, _window_torch(prob, radius, index)
+
+
+def disp_mode_torch(cost: torch.Tensor, maxdisp: int, radius: int, size=None, index=None):
+    """Plain-torch twin of ops.disp_softargmin_mode in cost's dtype and on its device: the upsampled cost v and p = softmin(v) of
+    disp_stats_torch, k* = the first arg-min of v (or `index`), then the window sums of p about k*.  Returns (disp, stats, mode)."""
+    import torch.nn.functional as F
+    if cost.dim() == 4:
+        cost = cost[:, None]
+    Ho, Wo = (3 * cost.shape[3], 3 * cost.shape[4]) if size is None else size
+    v = F.interpolate(cost, (int(maxdisp), int(Ho), int(Wo)), mode="trilinear", align_corners=False)[:, 0]
+    p = F.softmin(v, dim=1)
+    disp, stats = prob_stats_torch(p)
+    if index is None:
+        index = _first_index(v, v.amin(1, keepdim=True))
+    return disp, stats, _window_torch(p, radius, index)
+
+
 class MaskedSmoothL1Fn(torch.autograd.Function):
     """F.smooth_l1_loss(disp_est[mask], disp_gt[mask]) with mask = 0 < gt < maxdisp (rag.py:210-211), forward and
     backward in one kernel each, without the boolean gather (no stream synchronisation)."""

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import autograd as ag
 from . import ops
-from .metrics import DispStats, refuse_autograd
+from .metrics import MODE_RADIUS, DispMode, DispStats, refuse_autograd
 
 # src/automl/genotypes_2d.py:4-8 — the genotype handed to Network / Cell_3d; 3-D cells read `.reduce`
 Genotype = namedtuple("Genotype_2D", "normal normal_concat reduce reduce_concat")
@@ -317,6 +317,13 @@ class DisparityRegression(nn.Module):
         refuse_autograd("DisparityRegression.forward_stats", x)
         return DispStats(*ops.disparity_regression_stats(x, self.maxdisp, out, stats))
 
+    def forward_mode(self, x, radius=MODE_RADIUS, out=None, stats=None, mode=None):
+        """forward_stats with the first arg-max of x's disparity axis, the regression over |k - arg-max| <= radius and that window's
+        mass in the same launch -> DispMode; inference only."""
+        assert x.is_contiguous() is True
+        refuse_autograd("DisparityRegression.forward_mode", x)
+        return DispMode(*ops.disparity_regression_mode(x, self.maxdisp, radius, out, stats, mode), radius)
+
 
 class Disp(nn.Module):
     """src/models/rag_model.py:32-44, fused: trilinear x3 (align_corners=False) -> Softmin -> regression."""
@@ -337,6 +344,13 @@ class Disp(nn.Module):
         (.disp is forward's result bit for bit); inference only.  `out` / `stats`: caller-owned outputs (a captured graph's)."""
         refuse_autograd("Disp.forward_stats", x)
         return DispStats(*ops.disp_softargmin_stats(x, self.maxdisp, out, stats))
+
+    def forward_mode(self, x, radius=MODE_RADIUS, out=None, stats=None, mode=None):
+        """forward_stats with the mode-local disparity in the same launch -> DispMode: .mode_index is the fine index of the smallest
+        upsampled cost, .mode_disp the regression over |k - index| <= radius (on one surface where .disp averages two at a depth
+        edge), .mode_mass the probability of that window; .disp and .tensor are forward_stats' bits.  Inference only."""
+        refuse_autograd("Disp.forward_mode", x)
+        return DispMode(*ops.disp_softargmin_mode(x, self.maxdisp, radius, out, stats, mode), radius)
 
     def forward_train_stats(self, x):
         """forward_stats under autograd -> DispStats whose .disp and .tensor carry the graph (ag.DispStatsFn: the adjoint of the
@@ -1135,6 +1149,17 @@ class MatchingNet(nn.Module):
         with torch.no_grad():
             cost = self.matching(None, task_arch, None, features=(left_fea, right_fea))
             return self.disp.forward_stats(cost, out, stats)
+
+    def forward_mode(self, left_fea, right_fea, task_arch=None, radius=MODE_RADIUS, out=None, stats=None, mode=None):
+        """forward with the head's mode launch in place of the plain one -> DispMode; inference only."""
+        refuse_autograd("MatchingNet.forward_mode", left_fea, right_fea)
+        if task_arch is None:
+            task_arch = self.arch_init
+        if left_fea.shape != right_fea.shape or left_fea.dim() != 4:
+            raise ValueError("MatchingNet: left/right features must both be [B, C, h, w]")
+        with torch.no_grad():
+            cost = self.matching(None, task_arch, None, features=(left_fea, right_fea))
+            return self.disp.forward_mode(cost, radius, out, stats, mode)
 
     def forward_train_stats(self, left_fea, right_fea, task_arch=None):
         """forward under autograd with the head's statistics launch and its adjoint (Disp.forward_train_stats) -> DispStats whose

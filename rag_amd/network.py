@@ -19,7 +19,7 @@ from typing import Dict, List
 import torch
 import torch.nn as nn
 
-from .metrics import refuse_autograd
+from .metrics import MODE_RADIUS, refuse_autograd
 from .modules import Cell_2d, Cell_3d, ConvBR_2d, ConvBR_3d, MatchingNet, _ConvBR  # noqa: F401
 
 # Feature-Net macro architecture, rag_model.py:207-219: (prev_prev_fm, prev_fm, filter_multiplier, downup)
@@ -182,6 +182,24 @@ class Network(MatchingNet):
             lf, rf = self._features(left, right, lambda x: self.search_feature(x, selected_ops))
             cost = self.search_matching(None, selected_ops, t, features=(lf, rf))
             return self.disp.forward_stats(cost, out, stats)
+
+    def forward_mode(self, left, right, t, task_arch=None, path=None, radius=MODE_RADIUS, out=None, stats=None, mode=None):
+        """forward with the head's mode launch in place of the plain one -> DispMode (a DispStats with .mode_index / .mode_disp /
+        .mode_mass: the disparity regressed inside a window of `radius` fine px around the distribution's mode, and the probability
+        that window holds); inference only."""
+        refuse_autograd("Network.forward_mode", left, right)
+        with torch.no_grad():
+            lf, rf = self._features(left, right, lambda x: self.feature(x, task_arch, path))
+            cost = self.matching(None, task_arch, path, features=(lf, rf))
+            return self.disp.forward_mode(cost, radius, out, stats, mode)
+
+    def search_forward_mode(self, left, right, t, selected_ops, radius=MODE_RADIUS, out=None, stats=None, mode=None):
+        """search_forward with the head's mode launch -> DispMode; inference only."""
+        refuse_autograd("Network.search_forward_mode", left, right)
+        with torch.no_grad():
+            lf, rf = self._features(left, right, lambda x: self.search_feature(x, selected_ops))
+            cost = self.search_matching(None, selected_ops, t, features=(lf, rf))
+            return self.disp.forward_mode(cost, radius, out, stats, mode)
 
     # ------------------------------------------------------------------ the unit search's step (Appr.search_epoch, rag.py:344-406)
     def search_mode(self):

@@ -842,6 +842,63 @@ def disparity_regression_stats(prob: torch.Tensor, maxdisp: int, out: Optional[t
     return out, stats
 
 
+def _mode_check(what: str, B: int, H: int, W: int, maxdisp: int, radius, mode) -> int:
+    """The radius and a caller-owned `mode` of a mode launch, checked on the host before anything touches the device."""
+    if int(radius) != radius or not 0 <= int(radius) <= int(maxdisp):
+        raise ValueError(f"{what}: radius must be an integer in [0, maxdisp = {maxdisp}], got {radius!r}")
+    if mode is not None and (tuple(mode.shape) != (B, 3, H, W) or mode.dtype != torch.float32 or not mode.is_contiguous()):
+        raise ValueError(f"{what}: mode must be a contiguous [{B}, 3, {H}, {W}] fp32 tensor")
+    return int(radius)
+
+
+def _mode_outputs(what: str, ref: torch.Tensor, B: int, H: int, W: int, out, stats, mode):
+    """The three fp32 outputs of a mode launch: fresh, or the caller's own (a captured graph owns its outputs)."""
+    out, stats = _stats_outputs(what, ref, B, H, W, out, stats)
+    if mode is None:
+        mode = torch.empty((B, 3, H, W), device=ref.device, dtype=torch.float32)
+    _need_gpu(mode)
+    if mode.device != ref.device:
+        raise ValueError(f"{what}: mode must be on the input's device")
+    return out, stats, mode
+
+
+def disp_softargmin_mode(cost: torch.Tensor, maxdisp: int, radius: int, out: Optional[torch.Tensor] = None,
+                         stats: Optional[torch.Tensor] = None,
+                         mode: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """disp_softargmin_stats with the mode-local disparity, one launch: cost[B,1,d,h,w] (or [B,d,h,w]) -> (disparity [B,3h,3w] and stats
+    [B,3,3h,3w], the bits of disp_softargmin_stats, mode [B,3,3h,3w] = index k* of the smallest upsampled cost, disparity regressed over
+    |k - k*| <= radius about k*, probability mass of that window).  Inference only."""
+    if cost.dim() == 5:
+        if cost.shape[1] != 1:
+            raise ValueError("disp_softargmin_mode: expected a single-channel cost volume")
+        cost = cost[:, 0]
+    B, d, h, w = cost.shape
+    radius = _mode_check("disp_softargmin_mode", B, 3 * h, 3 * w, maxdisp, radius, mode)
+    dt = _act(cost)
+    cost = cost.contiguous()
+    out, stats, mode = _mode_outputs("disp_softargmin_mode", cost, B, 3 * h, 3 * w, out, stats, mode)
+    check(load_library().ragmi_disp_softargmin_mode_fwd(cost.data_ptr(), out.data_ptr(), stats.data_ptr(), mode.data_ptr(), B, d, h, w,
+                                                        int(maxdisp), 3 * h, 3 * w, radius, dt, _stream()), "disp_softargmin_mode")
+    return out, stats, mode
+
+
+def disparity_regression_mode(prob: torch.Tensor, maxdisp: int, radius: int, out: Optional[torch.Tensor] = None,
+                              stats: Optional[torch.Tensor] = None,
+                              mode: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """disparity_regression_stats with the mode-local disparity of prob[B,D,H,W] taken as given: (out [B,H,W], stats [B,3,H,W], mode
+    [B,3,H,W] = first arg-max k*, k* + sum_W p (k - k*) / sum_W p, sum_W p over |k - k*| <= radius)."""
+    B, D, H, W = prob.shape
+    if D != maxdisp:
+        raise ValueError("disparity_regression_mode: prob.shape[1] must equal maxdisp")
+    radius = _mode_check("disparity_regression_mode", B, H, W, maxdisp, radius, mode)
+    dt = _act(prob)
+    assert prob.is_contiguous()
+    out, stats, mode = _mode_outputs("disparity_regression_mode", prob, B, H, W, out, stats, mode)
+    check(load_library().ragmi_disparity_regression_mode_fwd(prob.data_ptr(), out.data_ptr(), stats.data_ptr(), mode.data_ptr(), B, D, H, W,
+                                                             radius, dt, _stream()), "disparity_regression_mode")
+    return out, stats, mode
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # training-step pieces (fp32): thin wrappers over the train.hip entry points; rag_amd/autograd.py composes them
 def _vol(t: torch.Tensor) -> int:
