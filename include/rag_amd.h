@@ -370,6 +370,29 @@ int ragmi_upconv3d_c1_fwd(const void* x, int64_t x_bstride, const void* weight, 
 int ragmi_trilinear3d_act_fwd(const void* x, int64_t x_bstride, void* y, int64_t y_bstride, int y_ch0, int relu, int B, int C,
                               int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners, int dtype, void* stream);
 
+/* The same head with the channel sum taken BEFORE the x2 upsample (rag_model.py:269, 357-365).  `upsample_6` is linear and acts per
+ * channel and last_3_3d has one output channel, so
+ *   last_3_3d(upsample2(y6))(v) = sum_t upsample2(P_t)(v + tap_t - 1),   P_t = sum_c w[c, t] * y6_c,   t = dz*9 + dy*3 + dx,
+ * with the convolution's zero padding unchanged (positions outside the upsampled volume contribute zero).  Two launches:
+ *
+ * ragmi_trilinear3d_act_k1_fwd = ragmi_trilinear3d_act_fwd followed, in registers, by a bias-free 1x1x1 channel mix:
+ *   y[b, y_ch0 + co] = sum_c weight[co, c] * act(interp(x)[b, c])     (c ascending, fp32 FMAs; the resampled channels are not stored)
+ * weight: fp32 [Cout][C], or [C][Cout] with w_transposed != 0 — the head passes last_3_3d's raw [1, C, 3, 3, 3] weight as
+ * [C][27].  The values entering the mix are bit-identical to what ragmi_trilinear3d_act_fwd stores.  fp32 only; supported: C <= 64,
+ * Cout <= 32 and an up-sampling by two or more on every axis (scale <= 0.5).
+ *
+ * ragmi_uptaps3d_fwd: p = P [B, 27, Di, Hi, Wi] fp32 (batch stride p_bstride) ->
+ *   y[:, y_ch0] = act(scale * sum_t upsample2(P_t)(v + tap_t - 1) + shift)   of [B, *, 2Di, 2Hi, 2Wi] fp32 (scale/shift optional),
+ * upsample2 = trilinear, align_corners=True, with the fp32 source-index rule of ragmi_trilinear3d_fwd (nesting x, y, z).
+ * supported: every input axis >= 2, even Wi, 27*Di*Hi*Wi < 2^31. */
+int ragmi_trilinear3d_act_k1_supported(int C, int Cout, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners);
+int ragmi_trilinear3d_act_k1_fwd(const void* x, int64_t x_bstride, const void* weight, int w_transposed, void* y, int64_t y_bstride,
+                                 int y_ch0, int relu, int B, int C, int Cout, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
+                                 int align_corners, int dtype, void* stream);
+int ragmi_uptaps3d_supported(int Di, int Hi, int Wi);
+int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* scale, const void* shift, int relu, void* y, int64_t y_bstride,
+                       int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream);
+
 /*
  * Feature-Net stem: 2-D 3x3 / pad 1 / stride `stride` ConvBR (stem2d1 = ConvBR_2d(6, 12, 3,
  * stride=3, padding=1), rag_model.py:201).  x: [B, Cin, H, W] -> y: [B, Cout, (H-1)/stride+1, (W-1)/stride+1].

@@ -97,6 +97,12 @@ SIGNATURES = {
                                       c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_trilinear3d_act_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_int, c_void_p]),
+    "ragmi_trilinear3d_act_k1_supported": (c_int, [c_int] * 9),
+    "ragmi_trilinear3d_act_k1_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                             c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ragmi_uptaps3d_supported": (c_int, [c_int, c_int, c_int]),
+    "ragmi_uptaps3d_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_void_p]),
     "ragmi_trilinear3d_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_int, c_void_p]),
     "ragmi_conv2d_k3_strided_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,

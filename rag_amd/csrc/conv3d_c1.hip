@@ -399,7 +399,248 @@ static int upconv_launch_typed(CUArgs a, hipStream_t st) {
   return check_launch("upconv3d_c1");
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The same head with the channel sum taken BEFORE the x2 upsample (rag_model.py:269, 357-365).  The upsample U is linear and acts
+// per channel and last_3_3d has one output channel, so
+//   mat(v) = sum_tap sum_c w[c, tap] U(y6_c)(v + tap) = sum_tap U(P_tap)(v + tap),   P_tap = sum_c w[c, tap] y6_c,
+// and the 27 single-channel level-6 volumes P_tap come out of the launch in front (trilinear_up_k1_kernel, resample.hip): 40 FMAs
+// per output voxel instead of 324, and no channel loop here.  upconv3d_c1_kernel interpolates a 4 x 6 operand window per plane and
+// CHANNEL (about 40 % of its instructions) before it multiplies; here the three blends are shared between the taps instead: for one
+// (dz, dy) the three dx volumes are blended along x AT LEVEL 6 and summed (a row of 4 outputs from 3 x 4 level-6 values), the three
+// dy of a dz are blended along y into the 2 x 4 outputs of a level-6 plane, and the three dz are blended along z into the ZSEG
+// output planes.  Nesting is therefore x, y, z (ATen's).
+// Every blend is written as weights over the thread's level-6 window (4 columns, 3 rows, UT_PZ planes) built from lin_index per
+// thread — a source pair that starts one lower than the x2 pattern (the last output of an axis in fp32) just moves its two weights
+// one slot down; positions outside the upsampled volume (the convolution's zero padding) get zero weights.
+// Frame as upconv3d_c1_kernel: 64 x 32 tile, 4 output planes, XCD-aware tile order; a stage is the THREE level-6 blocks of one
+// (dz, dy) (30 KB), double-buffered in LDS: the next stage's loads travel under this stage's arithmetic.
+constexpr int UT_TY = 64, UT_TX = 32, UT_THREADS = 256, UT_ZSEG = 4, UT_TAPS = 27;
+constexpr int UT_PZ = UT_ZSEG / 2 + 2, UT_PY = UT_TY / 2 + 2, UT_PX = UT_TX / 2 + 2, UT_RS = UT_PX + 2;   // block 4 x 34 x 18, row stride 20
+constexpr int UT_PLANE = UT_PY * UT_RS, UT_BLK = UT_PZ * UT_PLANE;
+constexpr int UT_NPF = (UT_PZ * UT_PY * UT_PX + UT_THREADS - 1) / UT_THREADS;      // 10 loads per thread and tap volume
+
+struct UTArgs {
+  const float* x;          // P [B, 27, Di, Hi, Wi]
+  const float* scale;
+  const float* shift;
+  float* y;                // [B, *, 2 Di, 2 Hi, 2 Wi]
+  int64_t x_bstride, y_bstride;
+  int y_ch0, relu;
+  int B, Di, Hi, Wi;
+  float sd, sh, sw;
+  int tiles_x, tiles_y, nseg, nwork;
+};
+
+__global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
+  constexpr int ZSEG = UT_ZSEG, NP = ZSEG + 2;
+  __shared__ __attribute__((aligned(16))) float blk[2][3 * UT_BLK];
+  const int tid = threadIdx.x, tx = tid & 7, ty = tid >> 3;
+  const int D = 2 * a.Di, H = 2 * a.Hi, W = 2 * a.Wi;
+  const int chunk = (a.nwork + 7) / 8, j = blockIdx.x;      // XCD-aware order (as conv3d_c1_kernel)
+  int t = (j & 7) * chunk + (j >> 3);
+  if ((j >> 3) >= chunk || t >= a.nwork) return;
+  const int x0 = (t % a.tiles_x) * UT_TX; t /= a.tiles_x;
+  const int y0 = (t % a.tiles_y) * UT_TY; t /= a.tiles_y;
+  const int seg = t % a.nseg, b = t / a.nseg;
+  const int zs = seg * ZSEG, ze = min(D, zs + ZSEG);
+  const int HWi = a.Hi * a.Wi;
+  const int64_t DHWi = (int64_t)HWi * a.Di;
+  const int pz0 = zs / 2 - 1, py0 = y0 / 2 - 1, px0 = x0 / 2 - 1;      // block origin (coordinates clamped into the tensor at the load)
+  int soff[UT_NPF], doff[UT_NPF];
+#pragma unroll
+  for (int p = 0; p < UT_NPF; ++p) {
+    const int e = min(tid + p * UT_THREADS, UT_PZ * UT_PY * UT_PX - 1);
+    const int cx = e % UT_PX, cy = (e / UT_PX) % UT_PY, cz = e / (UT_PX * UT_PY);
+    soff[p] = min(max(pz0 + cz, 0), a.Di - 1) * HWi + min(max(py0 + cy, 0), a.Hi - 1) * a.Wi + min(max(px0 + cx, 0), a.Wi - 1);
+    doff[p] = (e / UT_PX) * UT_RS + cx;
+  }
+  const float* const xb = a.x + (int64_t)b * a.x_bstride;
+  float pf[3][UT_NPF];
+  auto prefetch = [&](int g) {                               // stage g: tap volumes 3g .. 3g + 2
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float* const pc = xb + (int64_t)min(3 * g + ch, UT_TAPS - 1) * DHWi;
+#pragma unroll
+      for (int p = 0; p < UT_NPF; ++p) pf[ch][p] = pc[soff[p]];
+    }
+  };
+  auto commit = [&](float* buf) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+      for (int p = 0; p < UT_NPF; ++p)
+        if (tid + p * UT_THREADS < UT_PZ * UT_PY * UT_PX) buf[ch * UT_BLK + doff[p]] = pf[ch][p];
+  };
+  // y: upsampled rows gy = y0 + 2ty - 1 + r, r = 0 .. 3 (2 output rows + halo), over block rows ty .. ty+2 (slots 0 .. 2).  The x2
+  // pattern puts r = 0, 1 on slots (0, 1) and r = 2, 3 on (1, 2), or one lower: (0, 1)
+  float wy[4][3];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int gy = y0 + 2 * ty - 1 + r, base = py0 + ty;
+    const LinIdx l = lin_index(min(max(gy, 0), H - 1), a.Hi, H, a.sh, 1);
+    const bool in = (unsigned)gy < (unsigned)H;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) wy[r][s] = in ? (l.i0 - base == s ? l.w0 : 0.f) + (l.i1 - base == s ? l.w1 : 0.f) : 0.f;
+  }
+  // x: upsampled columns gx = x0 + 4tx - 1 + u, u = 0 .. 5 (4 outputs + halo), over block columns 2tx .. 2tx+3 (slots 0 .. 3):
+  // u = 0, 1 on slots (0, 1); u = 2, 3 on (1, 2) or one lower; u = 4, 5 on (2, 3) or one lower.  wx[u][j]: slot xs(u) + j
+  float wx[6][3];
+#pragma unroll
+  for (int u = 0; u < 6; ++u) {
+    const int gx = x0 + 4 * tx - 1 + u, base = px0 + 2 * tx + (u >= 4 ? 1 : 0);
+    const LinIdx l = lin_index(min(max(gx, 0), W - 1), a.Wi, W, a.sw, 1);
+    const bool in = (unsigned)gx < (unsigned)W;
+#pragma unroll
+    for (int s = 0; s < 3; ++s) wx[u][s] = in ? (l.i0 - base == s ? l.w0 : 0.f) + (l.i1 - base == s ? l.w1 : 0.f) : 0.f;
+  }
+  // the block's first row enters the dy = 2 taps only where a row pair sits one lower (wave-uniform skip otherwise)
+  const bool row0_dy2 = __any(wy[2][0] != 0.f || wy[3][0] != 0.f);
+  // z (wave-uniform): upsampled plane z = zs - 1 + zi over block planes 0 .. UT_PZ-1; planes outside the volume or past the
+  // segment's last output plane + 1 contribute nothing
+  float wz[NP][UT_PZ];
+#pragma unroll
+  for (int zi = 0; zi < NP; ++zi) {
+    const int z = zs - 1 + zi;
+    const bool live = z >= 0 && z <= min(ze, D - 1);
+    const LinIdx l = lin_index(min(max(z, 0), D - 1), a.Di, D, a.sd, 1);
+#pragma unroll
+    for (int p = 0; p < UT_PZ; ++p)
+      wz[zi][p] = live ? (l.i0 - pz0 == p ? l.w0 : 0.f) + (l.i1 - pz0 == p ? l.w1 : 0.f) : 0.f;
+  }
+  float acc[ZSEG][2][4];
+#pragma unroll
+  for (int k = 0; k < ZSEG; ++k)
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[k][r][i] = 0.f;
+  prefetch(0);
+  commit(blk[0]);
+  __syncthreads();
+  const int wbase = ty * UT_RS + 2 * tx;                    // this thread's window in a block plane (floats; even: 8-byte reads)
+  static_for<3>([&](auto dz_) {
+    constexpr int dz = decltype(dz_)::value;
+    // output plane zs + k reads upsampled plane index zi = k + dz through this dz
+    bool need[UT_PZ];
+#pragma unroll
+    for (int p = 0; p < UT_PZ; ++p) {
+      need[p] = false;
+#pragma unroll
+      for (int k = 0; k < ZSEG; ++k) need[p] = need[p] || (zs + k < ze && wz[k + dz][p] != 0.f);
+    }
+    float R[UT_PZ][2][4];                                   // sum over dy, dx of the taps of this dz, blended along x and y
+#pragma unroll
+    for (int p = 0; p < UT_PZ; ++p)
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) R[p][r][i] = 0.f;
+    static_for<3>([&](auto dy_) {
+      constexpr int dy = decltype(dy_)::value, g = dz * 3 + dy;
+      const float* const cur = blk[g & 1];
+      if constexpr (g + 1 < 9) prefetch(g + 1);
+      static_for<UT_PZ>([&](auto p_) {
+        constexpr int p = decltype(p_)::value;
+        if (need[p]) {
+          static_for<3>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;          // block row ty + s; output rows r = ro + dy
+            if constexpr (!(dy == 0 && s == 2)) {
+              if (dy < 2 || s > 0 || row0_dy2) {
+                float Q[4];
+#pragma unroll
+                for (int dx = 0; dx < 3; ++dx) {
+                  const float* const q = cur + dx * UT_BLK + p * UT_PLANE + s * UT_RS + wbase;
+                  const float2 v0 = *reinterpret_cast<const float2*>(q), v1 = *reinterpret_cast<const float2*>(q + 2);
+                  const float v[4] = {v0.x, v0.y, v1.x, v1.y};
+#pragma unroll
+                  for (int i = 0; i < 4; ++i) {
+                    const int u = i + dx, xs = u >= 4 ? 1 : 0;       // compile time
+                    float qv = dx == 0 ? wx[u][0] * v[xs] : fmaf(wx[u][0], v[xs], Q[i]);
+                    qv = fmaf(wx[u][1], v[xs + 1], qv);
+                    if (u >= 2) qv = fmaf(wx[u][2], v[xs + 2], qv);
+                    Q[i] = qv;
+                  }
+                }
+#pragma unroll
+                for (int ro = 0; ro < 2; ++ro) {
+                  const int r = ro + dy;
+                  if (r < 2 && s == 2) continue;
+#pragma unroll
+                  for (int i = 0; i < 4; ++i) R[p][ro][i] = fmaf(wy[r][s], Q[i], R[p][ro][i]);
+                }
+              }
+            }
+          });
+        }
+      });
+      if constexpr (g + 1 < 9) commit(blk[(g + 1) & 1]);     // (the buffer stage g - 1 read: every thread left it before the last barrier)
+      __syncthreads();
+    });
+#pragma unroll
+    for (int p = 0; p < UT_PZ; ++p)
+#pragma unroll
+      for (int k = 0; k < ZSEG; ++k) {
+        const float wk = wz[k + dz][p];
+        if (zs + k < ze && wk != 0.f) {
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[k][r][i] = fmaf(wk, R[p][r][i], acc[k][r][i]);
+        }
+      }
+  });
+  const float sc = a.scale ? a.scale[0] : 1.f, sh = a.shift ? a.shift[0] : 0.f;
+  const int64_t HW = (int64_t)H * W;
+  float* const yb = a.y + (int64_t)b * a.y_bstride + (int64_t)a.y_ch0 * HW * D;
+  const int gx = x0 + 4 * tx;
+#pragma unroll
+  for (int k = 0; k < ZSEG; ++k) {
+    if (zs + k >= ze) continue;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int gy = y0 + 2 * ty + r;
+      if (gy >= H || gx >= W) continue;
+      float v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float u = fmaf(acc[k][r][i], sc, sh);
+        v[i] = a.relu ? fmaxf(u, 0.f) : u;
+      }
+      st4(yb + (int64_t)(zs + k) * HW + (int64_t)gy * W + gx, v);
+    }
+  }
+}
+
 }  // namespace ragmi
+
+extern "C" int ragmi_uptaps3d_supported(int Di, int Hi, int Wi) {
+  using namespace ragmi;
+  // as ragmi_upconv3d_c1_supported: whole 16-byte output rows, no axis of length 1, 32-bit offsets inside a sample
+  return (Di >= 2 && Hi >= 2 && Wi >= 2 && (2 * Wi) % 4 == 0 && (int64_t)UT_TAPS * Di * Hi * Wi < (1ll << 31)) ? 1 : 0;
+}
+
+extern "C" int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* scale, const void* shift, int relu, void* y,
+                                  int64_t y_bstride, int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(p && y, RAGMI_EINVAL, "uptaps3d: null pointer");
+  RAGMI_REQUIRE((scale == nullptr) == (shift == nullptr), RAGMI_EINVAL, "uptaps3d: scale/shift must both be given or both NULL");
+  RAGMI_REQUIRE(B > 0 && B <= 65535 && y_ch0 >= 0, RAGMI_EINVAL, "uptaps3d: bad size");
+  RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "uptaps3d: dtype %d not built (fp32 only)", dtype);
+  RAGMI_REQUIRE(ragmi_uptaps3d_supported(Di, Hi, Wi), RAGMI_EUNSUPPORTED, "uptaps3d: needs every input axis >= 2 and an even input width");
+  RAGMI_REQUIRE(y_bstride % 4 == 0 && aligned4(y, RAGMI_F32), RAGMI_EUNSUPPORTED, "uptaps3d: output rows must be 16-byte aligned");
+  UTArgs a{};
+  a.x = static_cast<const float*>(p); a.scale = static_cast<const float*>(scale); a.shift = static_cast<const float*>(shift);
+  a.y = static_cast<float*>(y);
+  a.x_bstride = p_bstride; a.y_bstride = y_bstride; a.y_ch0 = y_ch0; a.relu = relu ? 1 : 0;
+  a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi;
+  a.sd = lin_scale(Di, 2 * Di, 1); a.sh = lin_scale(Hi, 2 * Hi, 1); a.sw = lin_scale(Wi, 2 * Wi, 1);
+  a.tiles_x = (int)ceil_div(2 * Wi, UT_TX); a.tiles_y = (int)ceil_div(2 * Hi, UT_TY); a.nseg = (int)ceil_div(2 * Di, UT_ZSEG);
+  const int64_t nwork = (int64_t)a.tiles_x * a.tiles_y * a.nseg * B;
+  RAGMI_REQUIRE(nwork < (1ll << 28), RAGMI_EUNSUPPORTED, "uptaps3d: too many tiles");
+  a.nwork = (int)nwork;
+  hipLaunchKernelGGL(uptaps3d_kernel, dim3((unsigned)(ceil_div(nwork, 8) * 8)), dim3(UT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  return check_launch("uptaps3d");
+}
 
 extern "C" int ragmi_upconv3d_c1_supported(int Cin, int Di, int Hi, int Wi) {
   using namespace ragmi;

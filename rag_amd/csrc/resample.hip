@@ -140,6 +140,125 @@ __global__ __launch_bounds__(256) void trilinear_up_kernel(ResampleArgs a) {
   }
 }
 
+// trilinear_up_kernel followed by a bias-free 1x1x1 channel mix in registers: the C resampled (and optionally rectified) channels of
+// a voxel never reach memory, Cout <= 32 mixed channels do.  The head's use (rag_model.py:269, 357-365): upsample_6 is linear and
+// acts per channel and last_3_3d has ONE output channel, so the channel sum of that 3x3x3 convolution commutes with the x2
+// interpolation — mixing last_6_3d's 12 channels into the 27 tap volumes P_t = sum_c w[c, t] y6_c HERE (324 FMAs per level-6
+// voxel, 40 per output voxel) leaves the full-resolution kernel (uptaps3d_kernel, conv3d_c1.hip) 27 shifted samples and no channel
+// loop.  Staging, tile and interpolation are trilinear_up_kernel's, so the values that enter the mix are the bits it stores; the
+// mix is plain fp32 FMAs over c ascending.  A thread keeps CO x 4 accumulators (CO = Cout rounded up to 28 or 32: whole 16-byte
+// broadcast reads of a channel's weight row, padded with zeros in LDS).
+constexpr int TK_MAX_C = 64, TK_MAX_CO = 32;
+
+struct ResampleK1Args {
+  ResampleArgs r;
+  const float* w;          // [Cout][C], or [C][Cout] with w_ci_major (the head: last_3_3d's raw [1, C, 3, 3, 3] weight, Cout = 27)
+  int Cout, w_ci_major;
+};
+
+template <int CO>
+__global__ __launch_bounds__(256, 2) void trilinear_up_k1_kernel(ResampleK1Args ka) {
+  const ResampleArgs& a = ka.r;
+  __shared__ float tu_tile[2][TU_CG * TU_PV];
+  __shared__ __attribute__((aligned(16))) float wl[TK_MAX_C * CO];
+  const int tid = threadIdx.x, tx = tid % TU_TX, ty = tid / TU_TX;
+  const int nbx = (a.Wo + TU_TX - 1) / TU_TX, nby = (a.Ho + TU_TY - 1) / TU_TY;
+  const int ox0 = ((int)blockIdx.x % nbx) * TU_TX, oy0 = ((int)blockIdx.x / nbx % nby) * TU_TY, oz0 = ((int)blockIdx.x / (nbx * nby)) * TU_TZ;
+  const int b = blockIdx.y;
+  const int pz0 = lin_index(oz0, a.Di, a.Do, a.sd, a.align).i0, py0 = lin_index(oy0, a.Hi, a.Ho, a.sh, a.align).i0,
+            px0 = lin_index(ox0, a.Wi, a.Wo, a.sw, a.align).i0;
+  const int64_t ivol = (int64_t)a.Di * a.Hi * a.Wi, ovol = (int64_t)a.Do * a.Ho * a.Wo;
+  const float* xp = static_cast<const float*>(a.x) + (int64_t)b * a.x_bstride;
+  for (int i = tid; i < a.C * CO; i += 256) {
+    const int c = i / CO, co = i % CO;
+    wl[i] = co < ka.Cout ? (ka.w_ci_major ? ka.w[c * ka.Cout + co] : ka.w[co * a.C + c]) : 0.f;
+  }
+  int soff[TU_NPF];
+#pragma unroll
+  for (int j = 0; j < TU_NPF; ++j) {
+    const int e = min(tid + j * 256, TU_CG * TU_PV - 1), c = min(e / TU_PV, a.C - 1), r = e % TU_PV;
+    const int gz = min(pz0 + r / (TU_PY * TU_PX), a.Di - 1), gy = min(py0 + r / TU_PX % TU_PY, a.Hi - 1), gx = min(px0 + r % TU_PX, a.Wi - 1);
+    soff[j] = (int)(c * ivol + ((int64_t)gz * a.Hi + gy) * a.Wi + gx);
+  }
+  float pf[TU_NPF];
+  auto prefetch = [&](int c0) {
+    const float* src = xp + (int64_t)min(c0, max(a.C - TU_CG, 0)) * ivol;
+#pragma unroll
+    for (int j = 0; j < TU_NPF; ++j) pf[j] = src[soff[j]];
+  };
+  auto commit = [&](float* buf) {
+#pragma unroll
+    for (int j = 0; j < TU_NPF; ++j)
+      if (tid + j * 256 < TU_CG * TU_PV) buf[tid + j * 256] = pf[j];
+  };
+  const int ox = min(ox0 + tx, a.Wo - 1), oy = min(oy0 + ty, a.Ho - 1);
+  const LinIdx ly = lin_index(oy, a.Hi, a.Ho, a.sh, a.align);
+  const LinIdx lx = lin_index(ox, a.Wi, a.Wo, a.sw, a.align);
+  const int o00 = (ly.i0 - py0) * TU_PX + (lx.i0 - px0), o01 = o00 + (lx.i1 - lx.i0);
+  const int o10 = o00 + (ly.i1 - ly.i0) * TU_PX, o11 = o10 + (lx.i1 - lx.i0);
+  LinIdx lz[TU_TZ];
+#pragma unroll
+  for (int k = 0; k < TU_TZ; ++k) lz[k] = lin_index(min(oz0 + k, a.Do - 1), a.Di, a.Do, a.sd, a.align);
+  const bool inside = ox0 + tx < a.Wo && oy0 + ty < a.Ho;
+  float acc[CO][TU_TZ];
+#pragma unroll
+  for (int co = 0; co < CO; ++co)
+#pragma unroll
+    for (int k = 0; k < TU_TZ; ++k) acc[co][k] = 0.f;
+  const int ng = (a.C + TU_CG - 1) / TU_CG;
+  prefetch(0);
+  commit(tu_tile[0]);
+  __syncthreads();                                                           // (also publishes wl)
+  for (int g = 0; g < ng; ++g) {
+    if (g + 1 < ng) prefetch((g + 1) * TU_CG);
+    const float* buf = tu_tile[g & 1];
+    const int cbase = min(g * TU_CG, max(a.C - TU_CG, 0));
+#pragma unroll
+    for (int cc = 0; cc < TU_CG; ++cc) {
+      const int c = cbase + cc;
+      if (c < g * TU_CG || c >= a.C) continue;                               // channels enter the mix once, in ascending order
+      const float* t = buf + cc * TU_PV;
+      float pl[TU_PZ];
+#pragma unroll
+      for (int p = 0; p < TU_PZ; ++p) {
+        const float* q = t + p * (TU_PY * TU_PX);
+        pl[p] = lerp2(ly.w0, lerp2(lx.w0, q[o00], lx.w1, q[o01]), ly.w1, lerp2(lx.w0, q[o10], lx.w1, q[o11]));
+      }
+      float v[TU_TZ];
+#pragma unroll
+      for (int k = 0; k < TU_TZ; ++k) {
+        const int i0 = lz[k].i0 - pz0, i1 = lz[k].i1 - pz0;
+        const float a0 = i0 == 0 ? pl[0] : i0 == 1 ? pl[1] : i0 == 2 ? pl[2] : pl[3];
+        const float a1 = i1 == 0 ? pl[0] : i1 == 1 ? pl[1] : i1 == 2 ? pl[2] : pl[3];
+        const float u = lerp2(lz[k].w0, a0, lz[k].w1, a1);
+        v[k] = a.relu ? fmaxf(u, 0.f) : u;
+      }
+      const float4* const wq = reinterpret_cast<const float4*>(wl + c * CO);  // same address in every lane: broadcast reads
+#pragma unroll
+      for (int q = 0; q < CO / 4; ++q) {
+        const float4 m = wq[q];
+#pragma unroll
+        for (int k = 0; k < TU_TZ; ++k) {
+          acc[4 * q][k] = fmaf(m.x, v[k], acc[4 * q][k]);
+          acc[4 * q + 1][k] = fmaf(m.y, v[k], acc[4 * q + 1][k]);
+          acc[4 * q + 2][k] = fmaf(m.z, v[k], acc[4 * q + 2][k]);
+          acc[4 * q + 3][k] = fmaf(m.w, v[k], acc[4 * q + 3][k]);
+        }
+      }
+    }
+    if (g + 1 < ng) commit(tu_tile[(g + 1) & 1]);
+    __syncthreads();
+  }
+  if (!inside) return;
+  float* yp = static_cast<float*>(a.y) + (int64_t)b * a.y_bstride + (int64_t)a.y_ch0 * ovol + ((int64_t)oz0 * a.Ho + oy) * a.Wo + ox;
+  const int64_t zs = (int64_t)a.Ho * a.Wo;
+#pragma unroll
+  for (int co = 0; co < CO; ++co)
+#pragma unroll
+    for (int k = 0; k < TU_TZ; ++k)
+      if (co < ka.Cout && oz0 + k < a.Do) yp[co * ovol + k * zs] = acc[co][k];
+}
+
 }  // namespace ragmi
 
 static int trilinear_launch(const void* x, int64_t x_bstride, void* y, int64_t y_bstride, int y_ch0, int relu, int B, int C, int Di,
@@ -179,4 +298,34 @@ extern "C" int ragmi_trilinear3d_act_fwd(const void* x, int64_t x_bstride, void*
                                          int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners, int dtype, void* stream) {
   return trilinear_launch(x, x_bstride, y, y_bstride, y_ch0, relu, B, C, Di, Hi, Wi, Do, Ho, Wo, align_corners, dtype, stream,
                           "trilinear3d_act");
+}
+
+extern "C" int ragmi_trilinear3d_act_k1_supported(int C, int Cout, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners) {
+  using namespace ragmi;
+  if (C < 1 || C > TK_MAX_C || Cout < 1 || Cout > TK_MAX_CO || Di < 1 || Hi < 1 || Wi < 1 || Do < 1 || Ho < 1 || Wo < 1) return 0;
+  // the staged up-sampling kernel's own conditions (trilinear_launch): every scale <= 0.5, 32-bit block count and input offsets
+  const float sd = lin_scale(Di, Do, align_corners), sh = lin_scale(Hi, Ho, align_corners), sw = lin_scale(Wi, Wo, align_corners);
+  const int64_t nblk = ceil_div(Wo, TU_TX) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ);
+  return (sd <= 0.5f && sh <= 0.5f && sw <= 0.5f && nblk < (1ll << 31) && (int64_t)C * Di * Hi * Wi < (1ll << 31)) ? 1 : 0;
+}
+
+extern "C" int ragmi_trilinear3d_act_k1_fwd(const void* x, int64_t x_bstride, const void* weight, int w_transposed, void* y,
+                                            int64_t y_bstride, int y_ch0, int relu, int B, int C, int Cout, int Di, int Hi, int Wi, int Do,
+                                            int Ho, int Wo, int align_corners, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(x && weight && y, RAGMI_EINVAL, "trilinear3d_act_k1: null pointer");
+  RAGMI_REQUIRE(B > 0 && B <= 65535 && y_ch0 >= 0, RAGMI_EINVAL, "trilinear3d_act_k1: bad size");
+  RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "trilinear3d_act_k1: dtype %d not built (fp32 only)", dtype);
+  RAGMI_REQUIRE(ragmi_trilinear3d_act_k1_supported(C, Cout, Di, Hi, Wi, Do, Ho, Wo, align_corners), RAGMI_EUNSUPPORTED,
+                "trilinear3d_act_k1: needs 1..%d input and 1..%d output channels and an up-sampling by two or more on every axis",
+                TK_MAX_C, TK_MAX_CO);
+  ResampleK1Args ka{};
+  ka.r = ResampleArgs{x, y, C, Di, Hi, Wi, Do, Ho, Wo,
+                      lin_scale(Di, Do, align_corners), lin_scale(Hi, Ho, align_corners), lin_scale(Wi, Wo, align_corners),
+                      align_corners ? 1 : 0, x_bstride, y_bstride, y_ch0, relu ? 1 : 0};
+  ka.w = static_cast<const float*>(weight); ka.Cout = Cout; ka.w_ci_major = w_transposed ? 1 : 0;
+  const dim3 grid((unsigned)(ceil_div(Wo, TU_TX) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ)), B);
+  if (Cout <= 28) hipLaunchKernelGGL(trilinear_up_k1_kernel<28>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+  else hipLaunchKernelGGL(trilinear_up_k1_kernel<32>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+  return check_launch("trilinear3d_act_k1");
 }

@@ -923,15 +923,32 @@ def _plan_head(vol, last_size, last_dtype, m3, m6, m12, train: bool) -> _HeadPla
     return _HeadPlan(level, bool(cross), bool(chain), bool(upconv))
 
 
-def _head_quarter(last5, m12, m6, half, plan: _HeadPlan) -> torch.Tensor:
+def _plan_head_taps(plan: _HeadPlan, vol, last_size, last_dtype, m3, m6) -> bool:
+    """Whether the head takes last_3_3d's channel sum BEFORE upsample_6 (rag_model.py:269, 357-365): the 1/4-level step's resample
+    launch mixes last_6_3d's channels into the 27 tap volumes (ops.trilinear3d_act_k1) and ops.uptaps3d sums their 27 shifted x2
+    samples, instead of trilinear3d_act -> upconv3d_c1.  Only where `plan` ends the 1/4-level step in that resample launch (chain) and
+    runs the fused head kernel (upconv: inference, one output channel, exact factor 2) on an fp32 `low`.  Pure, like _plan_head."""
+    if not (ops.head_taps_enabled() and plan.level == 4 and plan.chain and plan.upconv and m3 is not None and m3.conv.out_channels == 1
+            and last_dtype == torch.float32):
+        return False
+    d, h, w = (int(v) for v in vol)
+    half = (d // 2, h // 2, w // 2)
+    return bool(ops.trilinear3d_act_k1_supported(m6.conv.out_channels, 27, tuple(int(v) for v in last_size), half, True)
+                and ops.uptaps3d_supported(*half))
+
+
+def _head_quarter(last5, m12, m6, half, plan: _HeadPlan, taps_weight=None) -> torch.Tensor:
     """The head's 1/4-level step, last_6_3d(upsample_12(last_12_3d(last5))) at `half` (upsample_12 is fused into last_6_3d's 1x1x1
-    kernel, conv-first), launched as `plan` says; shared by MatchingNet._head and depth.Network._trunk."""
+    kernel, conv-first), launched as `plan` says; shared by MatchingNet._head and depth.Network._trunk.  `taps_weight` (_plan_head_taps:
+    last_3_3d's raw [1, C, 3, 3, 3] weight): the resample launch returns that convolution's 27 tap volumes instead."""
     B, dev = last5.shape[0], last5.device
     if plan.chain:
         w1, s1, h1 = m12.prepared()
         w2, s2, h2 = m6.prepared()
         low = torch.empty((B, m6.conv.out_channels) + tuple(last5.shape[2:]), device=dev, dtype=last5.dtype)
         ops.conv3d_k1_chain(last5, w1, s1, h1, m12.relu, w2, s2, h2, False, low)
+        if taps_weight is not None:
+            return ops.trilinear3d_act_k1(low, half, True, m6.relu, taps_weight, transposed=True)
         y = torch.empty((B, m6.conv.out_channels) + tuple(half), device=dev, dtype=last5.dtype)
         ops.trilinear3d_act(low, half, True, m6.relu, y, 0)
         return y
@@ -1116,6 +1133,10 @@ class MatchingNet(nn.Module):
         if plan.level == 1:
             return m3(last_output, out_dtype=f32)
         d, h, w = vol
+        if _plan_head_taps(plan, vol, last_output.shape[2:], last_output.dtype, m3, m6):
+            wk, scale, shift = m3.prepared()             # the raw [1, C, 3, 3, 3] weight, read as the [C][27] channel mix
+            p6 = _head_quarter(last_output, m12, m6, (d // 2, h // 2, w // 2), plan, taps_weight=wk)
+            return ops.uptaps3d(p6, scale, shift, m3.relu)
         y = m6(last_output) if plan.level == 2 else _head_quarter(last_output, m12, m6, (d // 2, h // 2, w // 2), plan)
         if plan.upconv:         # the 12-channel full-resolution tensor is never written
             wk, scale, shift = m3.prepared()             # the raw [1, C, 3, 3, 3] weight (VALU forms read it as is)

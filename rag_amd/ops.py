@@ -758,6 +758,70 @@ def trilinear3d_act(x: torch.Tensor, size: Sequence[int], align_corners: bool, r
     return out
 
 
+_HEAD_TAPS = [os.environ.get("RAGMI_HEAD_TAPS", "1") != "0"]      # the DEFAULT, read once at import (A/B tooling)
+
+
+def set_head_taps(enabled: bool) -> None:
+    """Whether the head takes last_3_3d's channel sum before the x2 upsample (trilinear3d_act_k1 -> uptaps3d) instead of
+    trilinear3d_act -> upconv3d_c1.  Off: exactly those two launches."""
+    _HEAD_TAPS[0] = bool(enabled)
+
+
+def head_taps_enabled() -> bool:
+    return _HEAD_TAPS[0]
+
+
+def trilinear3d_act_k1_supported(c: int, cout: int, in_size: Sequence[int], out_size: Sequence[int], align_corners: bool) -> bool:
+    return bool(load_library().ragmi_trilinear3d_act_k1_supported(int(c), int(cout), *(int(v) for v in in_size), *(int(v) for v in out_size),
+                                                                    int(bool(align_corners))))
+
+
+def trilinear3d_act_k1(x: torch.Tensor, size: Sequence[int], align_corners: bool, relu: bool, weight: torch.Tensor,
+                       out: Optional[torch.Tensor] = None, out_ch0: int = 0, transposed: bool = False) -> torch.Tensor:
+    """out[:, out_ch0:out_ch0+Cout] = mix(act(F.interpolate(x, size, 'trilinear', align_corners))) with the bias-free 1x1x1 channel mix
+    `weight` ([Cout, C] elements; `transposed`: [C, Cout] elements, e.g. a raw [1, C, 3, 3, 3] conv weight as C x 27) applied in
+    registers: the resampled channels are not stored (ragmi_trilinear3d_act_k1_fwd).  float32; x may be a channel slice."""
+    _need_gpu(weight)
+    dt = _act(x) if out is None else _act(x, out)
+    B, C, Di, Hi, Wi = x.shape
+    Do, Ho, Wo = [int(s) for s in size]
+    if weight.dtype != torch.float32 or weight.numel() % C != 0:
+        raise ValueError("trilinear3d_act_k1: weight must be float32 with Cout * C elements")
+    Cout = weight.numel() // C
+    if out is None:
+        out = torch.empty((B, Cout, Do, Ho, Wo), device=x.device, dtype=x.dtype)
+    if out.shape[0] != B or out_ch0 < 0 or out_ch0 + Cout > out.shape[1] or tuple(out.shape[2:]) != (Do, Ho, Wo):
+        raise ValueError("trilinear3d_act_k1: output buffer too small / wrong spatial size")
+    check(load_library().ragmi_trilinear3d_act_k1_fwd(x.data_ptr(), _planes(x), weight.detach().contiguous().data_ptr(), int(bool(transposed)),
+                                                      out.data_ptr(), _planes(out), int(out_ch0), int(relu), B, C, Cout, Di, Hi, Wi,
+                                                      Do, Ho, Wo, int(bool(align_corners)), dt, _stream()), "trilinear3d_act_k1")
+    return out
+
+
+def uptaps3d_supported(di: int, hi: int, wi: int) -> bool:
+    return bool(load_library().ragmi_uptaps3d_supported(int(di), int(hi), int(wi)))
+
+
+def uptaps3d(p: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], relu: bool,
+             out: Optional[torch.Tensor] = None, out_ch0: int = 0) -> torch.Tensor:
+    """out[:, out_ch0] = act(scale * sum_t U(p[:, t])(v + tap_t - 1) + shift), U = F.interpolate(scale_factor=2, 'trilinear',
+    align_corners=True), t = dz*9 + dy*3 + dx, zero outside the upsampled volume: a one-output-channel 3x3x3 convolution of an
+    upsampled tensor whose channel sum was taken before the upsample (ragmi_uptaps3d_fwd).  p: float32 [B, 27, Di, Hi, Wi]."""
+    _need_gpu(scale, shift)
+    dt = _act(p) if out is None else _act(p, out)
+    B, T, Di, Hi, Wi = p.shape
+    if T != 27:
+        raise ValueError("uptaps3d: p must be [B, 27, Di, Hi, Wi]")
+    if out is None:
+        out = torch.empty((B, 1, 2 * Di, 2 * Hi, 2 * Wi), device=p.device, dtype=p.dtype)
+    if tuple(out.shape[2:]) != (2 * Di, 2 * Hi, 2 * Wi) or out.shape[0] != B or not 0 <= out_ch0 < out.shape[1]:
+        raise ValueError("uptaps3d: out must be [B, >= out_ch0 + 1, 2Di, 2Hi, 2Wi]")
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    check(load_library().ragmi_uptaps3d_fwd(p.data_ptr(), _planes(p), ptr(scale), ptr(shift), int(relu), out.data_ptr(), _planes(out),
+                                            int(out_ch0), B, Di, Hi, Wi, dt, _stream()), "uptaps3d")
+    return out
+
+
 def add(a: torch.Tensor, a_ch0: int, b: torch.Tensor, b_ch0: int, out: torch.Tensor, out_ch0: int, channels: int) -> torch.Tensor:
     """out[:, out_ch0:+C] = a[:, a_ch0:+C] + b[:, b_ch0:+C]."""
     dt = _act(a, b, out)

@@ -1,5 +1,6 @@
 """Time the head's last steps at the headline shape: y6 [1,12,32,64,208] -> upsample x2 -> last_3_3d (12 -> 1) -> mat [1,1,64,128,416].
-   (a) the fused kernel ragmi_upconv3d_c1_fwd; (b) standalone upsample + convolution (conv3d_c1 / generic small-Cout kernel).
+   (a) the fused kernel ragmi_upconv3d_c1_fwd; (b) standalone upsample + convolution (conv3d_c1 / generic small-Cout kernel);
+   (c) the tap form from level 12 (ragmi_trilinear3d_act_k1_fwd -> ragmi_uptaps3d_fwd) against the same two launches of the channel form.
     python tools/bench_head.py"""
 import os
 import sys
@@ -39,3 +40,26 @@ t_two = timed(two)
 t_fused = timed(lambda i: ra.ops.upconv3d_c1(y6, w, None, None, False, out))
 print(f"last_3_3d alone {t_conv:.1f} us; upsample + last_3_3d {t_two:.1f} us; fused upconv3d_c1 {t_fused:.1f} us "
       f"({2 * 27 * 12 * out.numel() / t_fused / 1e6:.1f} TFLOP/s)")
+
+# (c) the tap form from one level lower, as MatchingNet._head runs it: low [1,12,16,32,104] -> resample + ReLU (+ the 12 -> 27 mix) ->
+# head kernel, against the same two launches of the channel form (trilinear3d_act -> upconv3d_c1)
+low = torch.randn((1, 12, 16, 32, 104), device=dev)
+y6b = torch.empty_like(y6)
+p6 = torch.empty((1, 27) + tuple(y6.shape[2:]), device=dev)
+
+
+def channel_pair(i):
+    ra.ops.trilinear3d_act(low, y6.shape[2:], True, True, y6b, 0)
+    ra.ops.upconv3d_c1(y6b, w, None, None, False, out)
+
+
+def tap_pair(i):
+    ra.ops.trilinear3d_act_k1(low, y6.shape[2:], True, True, w, p6, 0, transposed=True)
+    ra.ops.uptaps3d(p6, None, None, False, out)
+
+
+t_ch, t_tap = timed(channel_pair), timed(tap_pair)
+t_k1 = timed(lambda i: ra.ops.trilinear3d_act_k1(low, y6.shape[2:], True, True, w, p6, 0, transposed=True))
+t_ut = timed(lambda i: ra.ops.uptaps3d(p6, None, None, False, out))
+print(f"head from level 12: trilinear3d_act + upconv3d_c1 {t_ch:.1f} us; trilinear3d_act_k1 + uptaps3d {t_tap:.1f} us "
+      f"(trilinear3d_act_k1 alone {t_k1:.1f} us, uptaps3d alone {t_ut:.1f} us)")
