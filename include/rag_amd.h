@@ -393,6 +393,27 @@ int ragmi_uptaps3d_supported(int Di, int Hi, int Wi);
 int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* scale, const void* shift, int relu, void* y, int64_t y_bstride,
                        int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream);
 
+/* The same two launches with the x blend of upsample_6 (rag_model.py:269, 357-365) moved into the first one.  The x-blended row of
+ * a (dz, dy) tap pair depends on global coordinates only,
+ *   Q[dz*3 + dy](z6, y6, gx) = sum over dx of upsample2_x(P[dz*9 + dy*3 + dx](z6, y6, .))(gx + dx - 1),   gx in [0, 2 Wo),
+ * (zero where gx + dx - 1 leaves the row), so it is formed once per level-6 voxel instead of once per output tile and segment.
+ *
+ * ragmi_trilinear3d_act_k1_xblend_fwd: ragmi_trilinear3d_act_k1_fwd with weight = last_3_3d's raw [1, C, 3, 3, 3] tensor read as
+ * [C][27]; the 27 P values of a voxel (the bits that launch stores) stay in registers and
+ *   q[b, q_ch0 + g] = Q[g]   of [B, *, Do, Ho, 2 Wo] fp32 (batch stride q_bstride, 8-byte aligned rows)
+ * leaves, two columns per level-6 voxel.  supported: ragmi_trilinear3d_act_k1_supported, Cout == 27 and Wo == 2 Wi.
+ *
+ * ragmi_uptaps3d_xblended_fwd: ragmi_uptaps3d_fwd from q = Q [B, 9, Di, Hi, 2 Wi] (16-byte aligned, q_bstride % 4 == 0) — the y and z
+ * blends, the scale / shift / ReLU epilogue.  Same fmaf chains in the same order as ragmi_uptaps3d_fwd: the pair's output has the
+ * bits of ragmi_trilinear3d_act_k1_fwd -> ragmi_uptaps3d_fwd.  supported: as ragmi_uptaps3d_supported. */
+int ragmi_trilinear3d_act_k1_xblend_supported(int C, int Cout, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners);
+int ragmi_trilinear3d_act_k1_xblend_fwd(const void* x, int64_t x_bstride, const void* weight, void* q, int64_t q_bstride, int q_ch0,
+                                        int relu, int B, int C, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners,
+                                        int dtype, void* stream);
+int ragmi_uptaps3d_xblended_supported(int Di, int Hi, int Wi);
+int ragmi_uptaps3d_xblended_fwd(const void* q, int64_t q_bstride, const void* scale, const void* shift, int relu, void* y,
+                                int64_t y_bstride, int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream);
+
 /*
  * Feature-Net stem: 2-D 3x3 / pad 1 / stride `stride` ConvBR (stem2d1 = ConvBR_2d(6, 12, 3,
  * stride=3, padding=1), rag_model.py:201).  x: [B, Cin, H, W] -> y: [B, Cout, (H-1)/stride+1, (W-1)/stride+1].

@@ -103,6 +103,12 @@ SIGNATURES = {
     "ragmi_uptaps3d_supported": (c_int, [c_int, c_int, c_int]),
     "ragmi_uptaps3d_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                                    c_int, c_void_p]),
+    "ragmi_trilinear3d_act_k1_xblend_supported": (c_int, [c_int] * 9),
+    "ragmi_trilinear3d_act_k1_xblend_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                    c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ragmi_uptaps3d_xblended_supported": (c_int, [c_int, c_int, c_int]),
+    "ragmi_uptaps3d_xblended_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_void_p]),
     "ragmi_trilinear3d_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_int, c_int, c_void_p]),
     "ragmi_conv2d_k3_strided_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -418,9 +418,15 @@ constexpr int UT_TY = 64, UT_TX = 32, UT_THREADS = 256, UT_ZSEG = 4, UT_TAPS = 2
 constexpr int UT_PZ = UT_ZSEG / 2 + 2, UT_PY = UT_TY / 2 + 2, UT_PX = UT_TX / 2 + 2, UT_RS = UT_PX + 2;   // block 4 x 34 x 18, row stride 20
 constexpr int UT_PLANE = UT_PY * UT_RS, UT_BLK = UT_PZ * UT_PLANE;
 constexpr int UT_NPF = (UT_PZ * UT_PY * UT_PX + UT_THREADS - 1) / UT_THREADS;      // 10 loads per thread and tap volume
+// XB (ragmi_uptaps3d_xblended_fwd): the x stage already ran in the launch in front (trilinear_up_k1_kernel<28, true>, resample.hip),
+// which wrote Q [B, 9, Di, Hi, 2 Wi] — for every (dz, dy) the three dx volumes blended along x and summed, the `Q[i]` of the x stage
+// below at full x resolution.  A stage is then ONE block of Q[g], UT_PZ planes x UT_PY rows x the tile's 32 columns: whole 128-byte
+// rows and no x halo, 16-byte loads, and a thread's four values of a row are one 16-byte LDS read.  Everything behind the x stage
+// (the skips, the y and z chains, the epilogue) is the same code.
+constexpr int UQ_BLK = UT_PZ * UT_PY * UT_TX, UQ_NPF = (UQ_BLK / 4 + UT_THREADS - 1) / UT_THREADS;      // 17 KB; 5 loads per thread
 
 struct UTArgs {
-  const float* x;          // P [B, 27, Di, Hi, Wi]
+  const float* x;          // P [B, 27, Di, Hi, Wi]; XB: Q [B, 9, Di, Hi, 2 Wi]
   const float* scale;
   const float* shift;
   float* y;                // [B, *, 2 Di, 2 Hi, 2 Wi]
@@ -431,9 +437,10 @@ struct UTArgs {
   int tiles_x, tiles_y, nseg, nwork;
 };
 
+template <bool XB>
 __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
   constexpr int ZSEG = UT_ZSEG, NP = ZSEG + 2;
-  __shared__ __attribute__((aligned(16))) float blk[2][3 * UT_BLK];
+  __shared__ __attribute__((aligned(16))) float blk[2][XB ? UQ_BLK : 3 * UT_BLK];
   const int tid = threadIdx.x, tx = tid & 7, ty = tid >> 3;
   const int D = 2 * a.Di, H = 2 * a.Hi, W = 2 * a.Wi;
   const int chunk = (a.nwork + 7) / 8, j = blockIdx.x;      // XCD-aware order (as conv3d_c1_kernel)
@@ -446,30 +453,53 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
   const int HWi = a.Hi * a.Wi;
   const int64_t DHWi = (int64_t)HWi * a.Di;
   const int pz0 = zs / 2 - 1, py0 = y0 / 2 - 1, px0 = x0 / 2 - 1;      // block origin (coordinates clamped into the tensor at the load)
-  int soff[UT_NPF], doff[UT_NPF];
+  constexpr int NPF = XB ? UQ_NPF : UT_NPF;
+  int soff[NPF], doff[NPF];
 #pragma unroll
-  for (int p = 0; p < UT_NPF; ++p) {
-    const int e = min(tid + p * UT_THREADS, UT_PZ * UT_PY * UT_PX - 1);
-    const int cx = e % UT_PX, cy = (e / UT_PX) % UT_PY, cz = e / (UT_PX * UT_PY);
-    soff[p] = min(max(pz0 + cz, 0), a.Di - 1) * HWi + min(max(py0 + cy, 0), a.Hi - 1) * a.Wi + min(max(px0 + cx, 0), a.Wi - 1);
-    doff[p] = (e / UT_PX) * UT_RS + cx;
+  for (int p = 0; p < NPF; ++p) {
+    if constexpr (XB) {      // element = 4 columns of a Q row (W % 4 == 0: a group is inside the row or past it; past it loads the last one)
+      const int e = min(tid + p * UT_THREADS, UQ_BLK / 4 - 1);
+      const int cx = e % (UT_TX / 4), cy = (e / (UT_TX / 4)) % UT_PY, cz = e / (UT_TX / 4 * UT_PY);
+      soff[p] = (min(max(pz0 + cz, 0), a.Di - 1) * a.Hi + min(max(py0 + cy, 0), a.Hi - 1)) * W + min(x0 + 4 * cx, W - 4);
+      doff[p] = 4 * e;
+    } else {
+      const int e = min(tid + p * UT_THREADS, UT_PZ * UT_PY * UT_PX - 1);
+      const int cx = e % UT_PX, cy = (e / UT_PX) % UT_PY, cz = e / (UT_PX * UT_PY);
+      soff[p] = min(max(pz0 + cz, 0), a.Di - 1) * HWi + min(max(py0 + cy, 0), a.Hi - 1) * a.Wi + min(max(px0 + cx, 0), a.Wi - 1);
+      doff[p] = (e / UT_PX) * UT_RS + cx;
+    }
   }
   const float* const xb = a.x + (int64_t)b * a.x_bstride;
-  float pf[3][UT_NPF];
-  auto prefetch = [&](int g) {                               // stage g: tap volumes 3g .. 3g + 2
+  float pf[XB ? UQ_NPF : 3][XB ? 4 : UT_NPF];                // XB: [load][column of the group]
+  auto prefetch = [&](int g) {                               // stage g: tap volumes 3g .. 3g + 2; XB: Q[g]
+    if constexpr (XB) {
+      const float* const pc = xb + (int64_t)g * (2 * DHWi);
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const float* const pc = xb + (int64_t)min(3 * g + ch, UT_TAPS - 1) * DHWi;
+      for (int p = 0; p < UQ_NPF; ++p) {
+        const float4 v = *reinterpret_cast<const float4*>(pc + soff[p]);
+        pf[p][0] = v.x; pf[p][1] = v.y; pf[p][2] = v.z; pf[p][3] = v.w;
+      }
+    } else {
 #pragma unroll
-      for (int p = 0; p < UT_NPF; ++p) pf[ch][p] = pc[soff[p]];
+      for (int ch = 0; ch < 3; ++ch) {
+        const float* const pc = xb + (int64_t)min(3 * g + ch, UT_TAPS - 1) * DHWi;
+#pragma unroll
+        for (int p = 0; p < UT_NPF; ++p) pf[ch][p] = pc[soff[p]];
+      }
     }
   };
   auto commit = [&](float* buf) {
+    if constexpr (XB) {
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
+      for (int p = 0; p < UQ_NPF; ++p)
+        if (tid + p * UT_THREADS < UQ_BLK / 4) *reinterpret_cast<float4*>(buf + doff[p]) = make_float4(pf[p][0], pf[p][1], pf[p][2], pf[p][3]);
+    } else {
 #pragma unroll
-      for (int p = 0; p < UT_NPF; ++p)
-        if (tid + p * UT_THREADS < UT_PZ * UT_PY * UT_PX) buf[ch * UT_BLK + doff[p]] = pf[ch][p];
+      for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+        for (int p = 0; p < UT_NPF; ++p)
+          if (tid + p * UT_THREADS < UT_PZ * UT_PY * UT_PX) buf[ch * UT_BLK + doff[p]] = pf[ch][p];
+    }
   };
   // y: upsampled rows gy = y0 + 2ty - 1 + r, r = 0 .. 3 (2 output rows + halo), over block rows ty .. ty+2 (slots 0 .. 2).  The x2
   // pattern puts r = 0, 1 on slots (0, 1) and r = 2, 3 on (1, 2), or one lower: (0, 1)
@@ -547,8 +577,12 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
             if constexpr (!(dy == 0 && s == 2)) {
               if (dy < 2 || s > 0 || row0_dy2) {
                 float Q[4];
+                if constexpr (XB) {
+                  const float4 v = *reinterpret_cast<const float4*>(cur + (p * UT_PY + ty + s) * UT_TX + 4 * tx);
+                  Q[0] = v.x; Q[1] = v.y; Q[2] = v.z; Q[3] = v.w;
+                }
 #pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
+                for (int dx = 0; dx < (XB ? 0 : 3); ++dx) {
                   const float* const q = cur + dx * UT_BLK + p * UT_PLANE + s * UT_RS + wbase;
                   const float2 v0 = *reinterpret_cast<const float2*>(q), v1 = *reinterpret_cast<const float2*>(q + 2);
                   const float v[4] = {v0.x, v0.y, v1.x, v1.y};
@@ -619,8 +653,9 @@ extern "C" int ragmi_uptaps3d_supported(int Di, int Hi, int Wi) {
   return (Di >= 2 && Hi >= 2 && Wi >= 2 && (2 * Wi) % 4 == 0 && (int64_t)UT_TAPS * Di * Hi * Wi < (1ll << 31)) ? 1 : 0;
 }
 
-extern "C" int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* scale, const void* shift, int relu, void* y,
-                                  int64_t y_bstride, int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream) {
+// xblended: p is Q [B, 9, Di, Hi, 2 Wi] (ragmi_uptaps3d_xblended_fwd), not P [B, 27, Di, Hi, Wi]
+static int uptaps_launch(const void* p, int64_t p_bstride, const void* scale, const void* shift, int relu, void* y, int64_t y_bstride,
+                         int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream, bool xblended) {
   using namespace ragmi;
   RAGMI_REQUIRE(p && y, RAGMI_EINVAL, "uptaps3d: null pointer");
   RAGMI_REQUIRE((scale == nullptr) == (shift == nullptr), RAGMI_EINVAL, "uptaps3d: scale/shift must both be given or both NULL");
@@ -628,6 +663,8 @@ extern "C" int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* 
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "uptaps3d: dtype %d not built (fp32 only)", dtype);
   RAGMI_REQUIRE(ragmi_uptaps3d_supported(Di, Hi, Wi), RAGMI_EUNSUPPORTED, "uptaps3d: needs every input axis >= 2 and an even input width");
   RAGMI_REQUIRE(y_bstride % 4 == 0 && aligned4(y, RAGMI_F32), RAGMI_EUNSUPPORTED, "uptaps3d: output rows must be 16-byte aligned");
+  RAGMI_REQUIRE(!xblended || (p_bstride % 4 == 0 && aligned4(p, RAGMI_F32)), RAGMI_EUNSUPPORTED,
+                "uptaps3d: x-blended input rows must be 16-byte aligned");
   UTArgs a{};
   a.x = static_cast<const float*>(p); a.scale = static_cast<const float*>(scale); a.shift = static_cast<const float*>(shift);
   a.y = static_cast<float*>(y);
@@ -638,8 +675,25 @@ extern "C" int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* 
   const int64_t nwork = (int64_t)a.tiles_x * a.tiles_y * a.nseg * B;
   RAGMI_REQUIRE(nwork < (1ll << 28), RAGMI_EUNSUPPORTED, "uptaps3d: too many tiles");
   a.nwork = (int)nwork;
-  hipLaunchKernelGGL(uptaps3d_kernel, dim3((unsigned)(ceil_div(nwork, 8) * 8)), dim3(UT_THREADS), 0, static_cast<hipStream_t>(stream), a);
-  return check_launch("uptaps3d");
+  const dim3 grid((unsigned)(ceil_div(nwork, 8) * 8));
+  if (xblended) hipLaunchKernelGGL(uptaps3d_kernel<true>, grid, dim3(UT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  else hipLaunchKernelGGL(uptaps3d_kernel<false>, grid, dim3(UT_THREADS), 0, static_cast<hipStream_t>(stream), a);
+  return check_launch(xblended ? "uptaps3d_xblended" : "uptaps3d");
+}
+
+extern "C" int ragmi_uptaps3d_fwd(const void* p, int64_t p_bstride, const void* scale, const void* shift, int relu, void* y,
+                                  int64_t y_bstride, int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream) {
+  return uptaps_launch(p, p_bstride, scale, shift, relu, y, y_bstride, y_ch0, B, Di, Hi, Wi, dtype, stream, false);
+}
+
+// The same sum from the x-blended rows Q [B, 9, Di, Hi, 2 Wi] of ragmi_trilinear3d_act_k1_xblend_fwd: the y and z blends only.
+extern "C" int ragmi_uptaps3d_xblended_supported(int Di, int Hi, int Wi) {
+  return ragmi_uptaps3d_supported(Di, Hi, Wi);      // (2 Wi % 4 == 0: Q's rows are whole 16-byte groups)
+}
+
+extern "C" int ragmi_uptaps3d_xblended_fwd(const void* q, int64_t q_bstride, const void* scale, const void* shift, int relu, void* y,
+                                           int64_t y_bstride, int y_ch0, int B, int Di, int Hi, int Wi, int dtype, void* stream) {
+  return uptaps_launch(q, q_bstride, scale, shift, relu, y, y_bstride, y_ch0, B, Di, Hi, Wi, dtype, stream, true);
 }
 
 extern "C" int ragmi_upconv3d_c1_supported(int Cin, int Di, int Hi, int Wi) {

@@ -148,25 +148,41 @@ __global__ __launch_bounds__(256) void trilinear_up_kernel(ResampleArgs a) {
 // loop.  Staging, tile and interpolation are trilinear_up_kernel's, so the values that enter the mix are the bits it stores; the
 // mix is plain fp32 FMAs over c ascending.  A thread keeps CO x 4 accumulators (CO = Cout rounded up to 28 or 32: whole 16-byte
 // broadcast reads of a channel's weight row, padded with zeros in LDS).
+// XB (the head, ragmi_trilinear3d_act_k1_xblend_fwd): the 27 P values do not leave either.  The x2 upsample's blend along x of the three
+// dx volumes of a (dz, dy) depends on global coordinates only and needs, for the two output columns of a level-6 voxel, that voxel's
+// and its two x neighbours' values (every width 2..600: tests/test_head_xblend.py) — so it is taken HERE, once per level-6 voxel,
+// instead of once per output tile and depth segment in uptaps3d_kernel, and the nine row volumes Q [B, 9, Do, Ho, 2 Wo] are stored.
 constexpr int TK_MAX_C = 64, TK_MAX_CO = 32;
 
 struct ResampleK1Args {
   ResampleArgs r;
   const float* w;          // [Cout][C], or [C][Cout] with w_ci_major (the head: last_3_3d's raw [1, C, 3, 3, 3] weight, Cout = 27)
   int Cout, w_ci_major;
+  float sq;                // XB: the x scale of the x2 upsample behind this launch, lin_scale(Wo, 2 Wo, 1) (uptaps3d_kernel's sw)
 };
 
-template <int CO>
+// the value lane - 1 / lane + 1 of this wave holds (the wave's first / last lane reads its own)
+__device__ __forceinline__ float lane_from_below(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x138, 0xf, 0xf, false));      // wave_shr:1
+}
+__device__ __forceinline__ float lane_from_above(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x130, 0xf, 0xf, false));      // wave_shl:1
+}
+
+template <int CO, bool XB>
 __global__ __launch_bounds__(256, 2) void trilinear_up_k1_kernel(ResampleK1Args ka) {
   const ResampleArgs& a = ka.r;
   __shared__ float tu_tile[2][TU_CG * TU_PV];
   __shared__ __attribute__((aligned(16))) float wl[TK_MAX_C * CO];
   const int tid = threadIdx.x, tx = tid % TU_TX, ty = tid / TU_TX;
-  const int nbx = (a.Wo + TU_TX - 1) / TU_TX, nby = (a.Ho + TU_TY - 1) / TU_TY;
-  const int ox0 = ((int)blockIdx.x % nbx) * TU_TX, oy0 = ((int)blockIdx.x / nbx % nby) * TU_TY, oz0 = ((int)blockIdx.x / (nbx * nby)) * TU_TZ;
+  // XB: tiles advance by TX_STEP = 30 columns and start one column early — columns 0 and 31 are the x halo of the 30 that store
+  constexpr int TX_STEP = XB ? TU_TX - 2 : TU_TX;
+  const int nbx = (a.Wo + TX_STEP - 1) / TX_STEP, nby = (a.Ho + TU_TY - 1) / TU_TY;
+  const int ox0 = ((int)blockIdx.x % nbx) * TX_STEP - (XB ? 1 : 0), oy0 = ((int)blockIdx.x / nbx % nby) * TU_TY,
+            oz0 = ((int)blockIdx.x / (nbx * nby)) * TU_TZ;
   const int b = blockIdx.y;
   const int pz0 = lin_index(oz0, a.Di, a.Do, a.sd, a.align).i0, py0 = lin_index(oy0, a.Hi, a.Ho, a.sh, a.align).i0,
-            px0 = lin_index(ox0, a.Wi, a.Wo, a.sw, a.align).i0;
+            px0 = lin_index(max(ox0, 0), a.Wi, a.Wo, a.sw, a.align).i0;
   const int64_t ivol = (int64_t)a.Di * a.Hi * a.Wi, ovol = (int64_t)a.Do * a.Ho * a.Wo;
   const float* xp = static_cast<const float*>(a.x) + (int64_t)b * a.x_bstride;
   for (int i = tid; i < a.C * CO; i += 256) {
@@ -191,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void trilinear_up_k1_kernel(ResampleK1Args 
     for (int j = 0; j < TU_NPF; ++j)
       if (tid + j * 256 < TU_CG * TU_PV) buf[tid + j * 256] = pf[j];
   };
-  const int ox = min(ox0 + tx, a.Wo - 1), oy = min(oy0 + ty, a.Ho - 1);
+  const int ox = min(max(ox0 + tx, 0), a.Wo - 1), oy = min(oy0 + ty, a.Ho - 1);      // (XB: the halo columns clamp into the volume)
   const LinIdx ly = lin_index(oy, a.Hi, a.Ho, a.sh, a.align);
   const LinIdx lx = lin_index(ox, a.Wi, a.Wo, a.sw, a.align);
   const int o00 = (ly.i0 - py0) * TU_PX + (lx.i0 - px0), o01 = o00 + (lx.i1 - lx.i0);
@@ -199,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void trilinear_up_k1_kernel(ResampleK1Args 
   LinIdx lz[TU_TZ];
 #pragma unroll
   for (int k = 0; k < TU_TZ; ++k) lz[k] = lin_index(min(oz0 + k, a.Do - 1), a.Di, a.Do, a.sd, a.align);
-  const bool inside = ox0 + tx < a.Wo && oy0 + ty < a.Ho;
+  const bool inside = ox0 + tx < a.Wo && oy0 + ty < a.Ho && (!XB || (tx >= 1 && tx <= TU_TX - 2));
   float acc[CO][TU_TZ];
 #pragma unroll
   for (int co = 0; co < CO; ++co)
@@ -249,14 +265,53 @@ __global__ __launch_bounds__(256, 2) void trilinear_up_k1_kernel(ResampleK1Args 
     if (g + 1 < ng) commit(tu_tile[(g + 1) & 1]);
     __syncthreads();
   }
-  if (!inside) return;
-  float* yp = static_cast<float*>(a.y) + (int64_t)b * a.y_bstride + (int64_t)a.y_ch0 * ovol + ((int64_t)oz0 * a.Ho + oy) * a.Wo + ox;
-  const int64_t zs = (int64_t)a.Ho * a.Wo;
+  if constexpr (XB) {
+    // Q[g](z, y, gx) for gx = 2 x6, 2 x6 + 1 and g = (dz, dy): uptaps3d_kernel's x stage, term for term — dx ascending, the window
+    // slots x6-1, x6, x6+1 ascending, the first term a product and every later one an fmaf (a zero-weight term leaves the sum as it
+    // is, so the slots that kernel's wider window adds or omits do not show).  The neighbours' P come from lanes tx -+ 1 of this
+    // wave (two rows of 32 lanes; lanes 0 and 31 of a row store nothing): every lane is still here.
+    const int x6 = ox0 + tx, W2 = 2 * a.Wo;
+    float wq[2][3][3];
 #pragma unroll
-  for (int co = 0; co < CO; ++co)
+    for (int j = 0; j < 2; ++j)
 #pragma unroll
-    for (int k = 0; k < TU_TZ; ++k)
-      if (co < ka.Cout && oz0 + k < a.Do) yp[co * ovol + k * zs] = acc[co][k];
+      for (int dx = 0; dx < 3; ++dx) {
+        const int gx = 2 * x6 + j + dx - 1, base = x6 - 1;
+        const LinIdx l = lin_index(min(max(gx, 0), W2 - 1), a.Wo, W2, ka.sq, 1);
+        const bool in = (unsigned)gx < (unsigned)W2;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) wq[j][dx][s] = in ? (l.i0 - base == s ? l.w0 : 0.f) + (l.i1 - base == s ? l.w1 : 0.f) : 0.f;
+      }
+    const int64_t qvol = 2 * ovol;
+    float* const yq = static_cast<float*>(a.y) + (int64_t)b * a.y_bstride + (int64_t)a.y_ch0 * qvol + ((int64_t)oz0 * a.Ho + oy) * W2 + 2 * x6;
+    const int64_t zs = (int64_t)a.Ho * W2;
+#pragma unroll
+    for (int g = 0; g < 9; ++g)
+#pragma unroll
+      for (int k = 0; k < TU_TZ; ++k) {
+        float q[2];
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const float c = acc[3 * g + dx][k], lo = lane_from_below(c), hi = lane_from_above(c);
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            float v = dx == 0 ? wq[j][0][0] * lo : fmaf(wq[j][dx][0], lo, q[j]);
+            v = fmaf(wq[j][dx][1], c, v);
+            q[j] = fmaf(wq[j][dx][2], hi, v);
+          }
+        }
+        if (inside && oz0 + k < a.Do) *reinterpret_cast<float2*>(yq + g * qvol + k * zs) = make_float2(q[0], q[1]);
+      }
+  } else {
+    if (!inside) return;
+    float* yp = static_cast<float*>(a.y) + (int64_t)b * a.y_bstride + (int64_t)a.y_ch0 * ovol + ((int64_t)oz0 * a.Ho + oy) * a.Wo + ox;
+    const int64_t zs = (int64_t)a.Ho * a.Wo;
+#pragma unroll
+    for (int co = 0; co < CO; ++co)
+#pragma unroll
+      for (int k = 0; k < TU_TZ; ++k)
+        if (co < ka.Cout && oz0 + k < a.Do) yp[co * ovol + k * zs] = acc[co][k];
+  }
 }
 
 }  // namespace ragmi
@@ -325,7 +380,41 @@ extern "C" int ragmi_trilinear3d_act_k1_fwd(const void* x, int64_t x_bstride, co
                       align_corners ? 1 : 0, x_bstride, y_bstride, y_ch0, relu ? 1 : 0};
   ka.w = static_cast<const float*>(weight); ka.Cout = Cout; ka.w_ci_major = w_transposed ? 1 : 0;
   const dim3 grid((unsigned)(ceil_div(Wo, TU_TX) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ)), B);
-  if (Cout <= 28) hipLaunchKernelGGL(trilinear_up_k1_kernel<28>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
-  else hipLaunchKernelGGL(trilinear_up_k1_kernel<32>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+  if (Cout <= 28) hipLaunchKernelGGL((trilinear_up_k1_kernel<28, false>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+  else hipLaunchKernelGGL((trilinear_up_k1_kernel<32, false>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
   return check_launch("trilinear3d_act_k1");
+}
+
+// The producer of the head's x-blended rows: as ragmi_trilinear3d_act_k1_fwd with last_3_3d's raw weight ([C][27], tap
+// index fastest), but the 27 tap volumes stay in registers and Q [B, 9, Do, Ho, 2 Wo] leaves: for every (dz, dy) the three dx volumes
+// blended along x by the x2 upsample (align_corners=True) that ragmi_uptaps3d_xblended_fwd completes along y and z.
+extern "C" int ragmi_trilinear3d_act_k1_xblend_supported(int C, int Cout, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int align_corners) {
+  using namespace ragmi;
+  if (Cout != 27 || !ragmi_trilinear3d_act_k1_supported(C, Cout, Di, Hi, Wi, Do, Ho, Wo, align_corners)) return 0;
+  // exact x2 along x: a tile's 32 columns (30 that store and their two neighbours) stay inside the staged 18 input columns
+  const int64_t nblk = ceil_div(Wo, TU_TX - 2) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ);
+  return (Wo == 2 * Wi && nblk < (1ll << 31) && (int64_t)18 * Do * Ho * Wo < (1ll << 31)) ? 1 : 0;
+}
+
+extern "C" int ragmi_trilinear3d_act_k1_xblend_fwd(const void* x, int64_t x_bstride, const void* weight, void* q, int64_t q_bstride,
+                                                   int q_ch0, int relu, int B, int C, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
+                                                   int align_corners, int dtype, void* stream) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(x && weight && q, RAGMI_EINVAL, "trilinear3d_act_k1_xblend: null pointer");
+  RAGMI_REQUIRE(B > 0 && B <= 65535 && q_ch0 >= 0, RAGMI_EINVAL, "trilinear3d_act_k1_xblend: bad size");
+  RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "trilinear3d_act_k1_xblend: dtype %d not built (fp32 only)", dtype);
+  RAGMI_REQUIRE(ragmi_trilinear3d_act_k1_xblend_supported(C, 27, Di, Hi, Wi, Do, Ho, Wo, align_corners), RAGMI_EUNSUPPORTED,
+                "trilinear3d_act_k1_xblend: needs 1..%d input channels, an up-sampling by two or more on every axis and by exactly two along x",
+                TK_MAX_C);
+  RAGMI_REQUIRE(q_bstride % 2 == 0 && reinterpret_cast<uintptr_t>(q) % 8 == 0, RAGMI_EUNSUPPORTED,
+                "trilinear3d_act_k1_xblend: output rows must be 8-byte aligned");
+  ResampleK1Args ka{};
+  ka.r = ResampleArgs{x, q, C, Di, Hi, Wi, Do, Ho, Wo,
+                      lin_scale(Di, Do, align_corners), lin_scale(Hi, Ho, align_corners), lin_scale(Wi, Wo, align_corners),
+                      align_corners ? 1 : 0, x_bstride, q_bstride, q_ch0, relu ? 1 : 0};
+  ka.w = static_cast<const float*>(weight); ka.Cout = 27; ka.w_ci_major = 1;
+  ka.sq = lin_scale(Wo, 2 * Wo, 1);
+  const dim3 grid((unsigned)(ceil_div(Wo, TU_TX - 2) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ)), B);
+  hipLaunchKernelGGL((trilinear_up_k1_kernel<28, true>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), ka);
+  return check_launch("trilinear3d_act_k1_xblend");
 }

@@ -937,10 +937,23 @@ def _plan_head_taps(plan: _HeadPlan, vol, last_size, last_dtype, m3, m6) -> bool
                 and ops.uptaps3d_supported(*half))
 
 
-def _head_quarter(last5, m12, m6, half, plan: _HeadPlan, taps_weight=None) -> torch.Tensor:
+def _plan_head_xblend(plan: _HeadPlan, vol, last_size, last_dtype, m3, m6) -> bool:
+    """Whether the tap form of the head (_plan_head_taps) blends the taps along x in the resample launch: it writes the nine x-blended
+    row volumes Q [B, 9, d/2, h/2, w] (ops.trilinear3d_act_k1(xblend=True)) and ops.uptaps3d(xblended=True) is left the y and z
+    blends.  Only where the tap form runs and both launches take the shape.  Pure, like _plan_head."""
+    if not (ops.head_xblend_enabled() and _plan_head_taps(plan, vol, last_size, last_dtype, m3, m6)):
+        return False
+    d, h, w = (int(v) for v in vol)
+    half = (d // 2, h // 2, w // 2)
+    return bool(ops.trilinear3d_act_k1_supported(m6.conv.out_channels, 27, tuple(int(v) for v in last_size), half, True, xblend=True)
+                and ops.uptaps3d_supported(*half, xblended=True))
+
+
+def _head_quarter(last5, m12, m6, half, plan: _HeadPlan, taps_weight=None, xblend: bool = False) -> torch.Tensor:
     """The head's 1/4-level step, last_6_3d(upsample_12(last_12_3d(last5))) at `half` (upsample_12 is fused into last_6_3d's 1x1x1
     kernel, conv-first), launched as `plan` says; shared by MatchingNet._head and depth.Network._trunk.  `taps_weight` (_plan_head_taps:
-    last_3_3d's raw [1, C, 3, 3, 3] weight): the resample launch returns that convolution's 27 tap volumes instead."""
+    last_3_3d's raw [1, C, 3, 3, 3] weight): the resample launch returns that convolution's 27 tap volumes instead, or with `xblend`
+    (_plan_head_xblend) their nine x-blended row volumes."""
     B, dev = last5.shape[0], last5.device
     if plan.chain:
         w1, s1, h1 = m12.prepared()
@@ -948,7 +961,7 @@ def _head_quarter(last5, m12, m6, half, plan: _HeadPlan, taps_weight=None) -> to
         low = torch.empty((B, m6.conv.out_channels) + tuple(last5.shape[2:]), device=dev, dtype=last5.dtype)
         ops.conv3d_k1_chain(last5, w1, s1, h1, m12.relu, w2, s2, h2, False, low)
         if taps_weight is not None:
-            return ops.trilinear3d_act_k1(low, half, True, m6.relu, taps_weight, transposed=True)
+            return ops.trilinear3d_act_k1(low, half, True, m6.relu, taps_weight, transposed=True, xblend=xblend)
         y = torch.empty((B, m6.conv.out_channels) + tuple(half), device=dev, dtype=last5.dtype)
         ops.trilinear3d_act(low, half, True, m6.relu, y, 0)
         return y
@@ -1135,8 +1148,9 @@ class MatchingNet(nn.Module):
         d, h, w = vol
         if _plan_head_taps(plan, vol, last_output.shape[2:], last_output.dtype, m3, m6):
             wk, scale, shift = m3.prepared()             # the raw [1, C, 3, 3, 3] weight, read as the [C][27] channel mix
-            p6 = _head_quarter(last_output, m12, m6, (d // 2, h // 2, w // 2), plan, taps_weight=wk)
-            return ops.uptaps3d(p6, scale, shift, m3.relu)
+            xb = _plan_head_xblend(plan, vol, last_output.shape[2:], last_output.dtype, m3, m6)      # p6: the x-blended rows Q
+            p6 = _head_quarter(last_output, m12, m6, (d // 2, h // 2, w // 2), plan, taps_weight=wk, xblend=xb)
+            return ops.uptaps3d(p6, scale, shift, m3.relu, xblended=xb)
         y = m6(last_output) if plan.level == 2 else _head_quarter(last_output, m12, m6, (d // 2, h // 2, w // 2), plan)
         if plan.upconv:         # the 12-channel full-resolution tensor is never written
             wk, scale, shift = m3.prepared()             # the raw [1, C, 3, 3, 3] weight (VALU forms read it as is)

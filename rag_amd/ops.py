@@ -771,16 +771,32 @@ def head_taps_enabled() -> bool:
     return _HEAD_TAPS[0]
 
 
-def trilinear3d_act_k1_supported(c: int, cout: int, in_size: Sequence[int], out_size: Sequence[int], align_corners: bool) -> bool:
-    return bool(load_library().ragmi_trilinear3d_act_k1_supported(int(c), int(cout), *(int(v) for v in in_size), *(int(v) for v in out_size),
-                                                                    int(bool(align_corners))))
+_HEAD_XBLEND = [os.environ.get("RAGMI_HEAD_XBLEND", "1") != "0"]      # the DEFAULT, read once at import (A/B tooling)
+
+
+def set_head_xblend(enabled: bool) -> None:
+    """Whether the tap form of the head blends the taps along x in the resample launch (trilinear3d_act_k1(xblend=True) ->
+    uptaps3d(xblended=True)).  Off: trilinear3d_act_k1 -> uptaps3d as they were."""
+    _HEAD_XBLEND[0] = bool(enabled)
+
+
+def head_xblend_enabled() -> bool:
+    return _HEAD_XBLEND[0]
+
+
+def trilinear3d_act_k1_supported(c: int, cout: int, in_size: Sequence[int], out_size: Sequence[int], align_corners: bool,
+                                 xblend: bool = False) -> bool:
+    fn = load_library().ragmi_trilinear3d_act_k1_xblend_supported if xblend else load_library().ragmi_trilinear3d_act_k1_supported
+    return bool(fn(int(c), int(cout), *(int(v) for v in in_size), *(int(v) for v in out_size), int(bool(align_corners))))
 
 
 def trilinear3d_act_k1(x: torch.Tensor, size: Sequence[int], align_corners: bool, relu: bool, weight: torch.Tensor,
-                       out: Optional[torch.Tensor] = None, out_ch0: int = 0, transposed: bool = False) -> torch.Tensor:
+                       out: Optional[torch.Tensor] = None, out_ch0: int = 0, transposed: bool = False, xblend: bool = False) -> torch.Tensor:
     """out[:, out_ch0:out_ch0+Cout] = mix(act(F.interpolate(x, size, 'trilinear', align_corners))) with the bias-free 1x1x1 channel mix
     `weight` ([Cout, C] elements; `transposed`: [C, Cout] elements, e.g. a raw [1, C, 3, 3, 3] conv weight as C x 27) applied in
-    registers: the resampled channels are not stored (ragmi_trilinear3d_act_k1_fwd).  float32; x may be a channel slice."""
+    registers: the resampled channels are not stored (ragmi_trilinear3d_act_k1_fwd).  float32; x may be a channel slice.
+    `xblend` (a transposed C x 27 weight): out[:, out_ch0:out_ch0+9] of [B, *, Do, Ho, 2 Wo] takes the x-blended rows Q of the 27 tap
+    volumes instead, the input of uptaps3d(xblended=True) (ragmi_trilinear3d_act_k1_xblend_fwd)."""
     _need_gpu(weight)
     dt = _act(x) if out is None else _act(x, out)
     B, C, Di, Hi, Wi = x.shape
@@ -788,6 +804,18 @@ def trilinear3d_act_k1(x: torch.Tensor, size: Sequence[int], align_corners: bool
     if weight.dtype != torch.float32 or weight.numel() % C != 0:
         raise ValueError("trilinear3d_act_k1: weight must be float32 with Cout * C elements")
     Cout = weight.numel() // C
+    if xblend:
+        if Cout != 27 or not transposed:
+            raise ValueError("trilinear3d_act_k1: xblend needs a transposed [C, 27] weight")
+        if out is None:
+            out = torch.empty((B, 9, Do, Ho, 2 * Wo), device=x.device, dtype=x.dtype)
+        if out.shape[0] != B or out_ch0 < 0 or out_ch0 + 9 > out.shape[1] or tuple(out.shape[2:]) != (Do, Ho, 2 * Wo):
+            raise ValueError("trilinear3d_act_k1: x-blended output buffer too small / wrong spatial size")
+        check(load_library().ragmi_trilinear3d_act_k1_xblend_fwd(x.data_ptr(), _planes(x), weight.detach().contiguous().data_ptr(),
+                                                                 out.data_ptr(), _planes(out), int(out_ch0), int(relu), B, C, Di, Hi, Wi,
+                                                                 Do, Ho, Wo, int(bool(align_corners)), dt, _stream()),
+              "trilinear3d_act_k1_xblend")
+        return out
     if out is None:
         out = torch.empty((B, Cout, Do, Ho, Wo), device=x.device, dtype=x.dtype)
     if out.shape[0] != B or out_ch0 < 0 or out_ch0 + Cout > out.shape[1] or tuple(out.shape[2:]) != (Do, Ho, Wo):
@@ -798,27 +826,34 @@ def trilinear3d_act_k1(x: torch.Tensor, size: Sequence[int], align_corners: bool
     return out
 
 
-def uptaps3d_supported(di: int, hi: int, wi: int) -> bool:
-    return bool(load_library().ragmi_uptaps3d_supported(int(di), int(hi), int(wi)))
+def uptaps3d_supported(di: int, hi: int, wi: int, xblended: bool = False) -> bool:
+    fn = load_library().ragmi_uptaps3d_xblended_supported if xblended else load_library().ragmi_uptaps3d_supported
+    return bool(fn(int(di), int(hi), int(wi)))
 
 
 def uptaps3d(p: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], relu: bool,
-             out: Optional[torch.Tensor] = None, out_ch0: int = 0) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, out_ch0: int = 0, xblended: bool = False) -> torch.Tensor:
     """out[:, out_ch0] = act(scale * sum_t U(p[:, t])(v + tap_t - 1) + shift), U = F.interpolate(scale_factor=2, 'trilinear',
     align_corners=True), t = dz*9 + dy*3 + dx, zero outside the upsampled volume: a one-output-channel 3x3x3 convolution of an
-    upsampled tensor whose channel sum was taken before the upsample (ragmi_uptaps3d_fwd).  p: float32 [B, 27, Di, Hi, Wi]."""
+    upsampled tensor whose channel sum was taken before the upsample (ragmi_uptaps3d_fwd).  p: float32 [B, 27, Di, Hi, Wi].
+    `xblended`: p is trilinear3d_act_k1(xblend=True)'s Q, float32 [B, 9, Di, Hi, 2 Wi] (ragmi_uptaps3d_xblended_fwd)."""
     _need_gpu(scale, shift)
     dt = _act(p) if out is None else _act(p, out)
     B, T, Di, Hi, Wi = p.shape
-    if T != 27:
+    if xblended:
+        if T != 9 or Wi % 2:
+            raise ValueError("uptaps3d: an x-blended p must be [B, 9, Di, Hi, 2 Wi]")
+        Wi //= 2
+    elif T != 27:
         raise ValueError("uptaps3d: p must be [B, 27, Di, Hi, Wi]")
     if out is None:
         out = torch.empty((B, 1, 2 * Di, 2 * Hi, 2 * Wi), device=p.device, dtype=p.dtype)
     if tuple(out.shape[2:]) != (2 * Di, 2 * Hi, 2 * Wi) or out.shape[0] != B or not 0 <= out_ch0 < out.shape[1]:
         raise ValueError("uptaps3d: out must be [B, >= out_ch0 + 1, 2Di, 2Hi, 2Wi]")
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    check(load_library().ragmi_uptaps3d_fwd(p.data_ptr(), _planes(p), ptr(scale), ptr(shift), int(relu), out.data_ptr(), _planes(out),
-                                            int(out_ch0), B, Di, Hi, Wi, dt, _stream()), "uptaps3d")
+    fwd = load_library().ragmi_uptaps3d_xblended_fwd if xblended else load_library().ragmi_uptaps3d_fwd
+    check(fwd(p.data_ptr(), _planes(p), ptr(scale), ptr(shift), int(relu), out.data_ptr(), _planes(out), int(out_ch0), B, Di, Hi, Wi, dt,
+              _stream()), "uptaps3d")
     return out
 
 

@@ -1,6 +1,7 @@
 """Time the head's last steps at the headline shape: y6 [1,12,32,64,208] -> upsample x2 -> last_3_3d (12 -> 1) -> mat [1,1,64,128,416].
    (a) the fused kernel ragmi_upconv3d_c1_fwd; (b) standalone upsample + convolution (conv3d_c1 / generic small-Cout kernel);
-   (c) the tap form from level 12 (ragmi_trilinear3d_act_k1_fwd -> ragmi_uptaps3d_fwd) against the same two launches of the channel form.
+   (c) the tap form from level 12 (ragmi_trilinear3d_act_k1_fwd -> ragmi_uptaps3d_fwd) against the same two launches of the channel form;
+   (d) the tap form with the x blend in the resample launch (ragmi_trilinear3d_act_k1_xblend_fwd -> ragmi_uptaps3d_xblended_fwd).
     python tools/bench_head.py"""
 import os
 import sys
@@ -63,3 +64,21 @@ t_k1 = timed(lambda i: ra.ops.trilinear3d_act_k1(low, y6.shape[2:], True, True, 
 t_ut = timed(lambda i: ra.ops.uptaps3d(p6, None, None, False, out))
 print(f"head from level 12: trilinear3d_act + upconv3d_c1 {t_ch:.1f} us; trilinear3d_act_k1 + uptaps3d {t_tap:.1f} us "
       f"(trilinear3d_act_k1 alone {t_k1:.1f} us, uptaps3d alone {t_ut:.1f} us)")
+
+# (d) the x blend of the taps taken in the resample launch: Q [1,9,32,64,416] between the two
+q6 = torch.empty((1, 9) + tuple(y6.shape[2:4]) + (2 * y6.shape[4],), device=dev)
+
+
+def xblend_pair(i):
+    ra.ops.trilinear3d_act_k1(low, y6.shape[2:], True, True, w, q6, 0, transposed=True, xblend=True)
+    ra.ops.uptaps3d(q6, None, None, False, out, xblended=True)
+
+
+tap_pair(0)
+ref = out.clone()
+xblend_pair(0)
+t_xb = timed(xblend_pair)
+t_xk1 = timed(lambda i: ra.ops.trilinear3d_act_k1(low, y6.shape[2:], True, True, w, q6, 0, transposed=True, xblend=True))
+t_xut = timed(lambda i: ra.ops.uptaps3d(q6, None, None, False, out, xblended=True))
+print(f"head from level 12, x blend in the resample launch: pair {t_xb:.1f} us (trilinear3d_act_k1 xblend alone {t_xk1:.1f} us, "
+      f"uptaps3d xblended alone {t_xut:.1f} us); output bits equal to the tap pair's: {torch.equal(out, ref)}")
