@@ -9,8 +9,10 @@
 // mu itself (known after the softmax walk), where the raw second moment would subtract two numbers of ~maxdisp^2.
 // The kernel keeps the shape of disp_softargmin_bwd_kernel (train.hip): a workgroup per 16 x 16 fine tile, the LDS tap table, the
 // barrier-separated tile reduction and one global add per coarse cell and plane; the statistics take a second walk over the fine
-// samples between the plain kernel's two passes.  The set-up and the flush are duplicated from train.hip, which is not touched.
-#include "common.h"
+// samples between the plain kernel's two passes.  Geometry, tap table and plane sampler are the shared parts of disp_common.h; the
+// walk loops, the softmax step and the tile reduction are written out as in train.hip, because their shared forms measured slower
+// here (profiles/disp_refactor_ab.json).
+#include "disp_common.h"
 
 namespace ragmi {
 
@@ -19,50 +21,39 @@ struct DispStatsBwdArgs {
   const float* dout;     // [B, Ho, Wo] or null
   const float* dstats;   // [B, 3, Ho, Wo] (variance, peak, entropy) or null
   float* dcost;
-  int d, h, w, maxdisp, Ho, Wo;
-  float sd, sh, sw;
+  DispGeom g;
 };
-constexpr int DS_T = 16, DS_WIN = 8;      // fine tile edge; coarse window edge (16/3 -> 6 cells + 1 each side for the taps)
 
 __global__ __launch_bounds__(256) void disp_softargmin_stats_bwd_kernel(DispStatsBwdArgs a) {
+  const DispGeom& g = a.g;
   extern __shared__ float4 ztab[];         // [maxdisp]: the fine-disparity taps, as in the forward kernel
-  __shared__ float pix[DS_T * DS_T], colsum[DS_T][DS_WIN], wxw[DS_T][DS_WIN], wyw[DS_T][DS_WIN];
+  __shared__ float pix[DISP_BWD_T * DISP_BWD_T], colsum[DISP_BWD_T][DISP_BWD_WIN];
+  __shared__ float wxw[DISP_BWD_T][DISP_BWD_WIN], wyw[DISP_BWD_T][DISP_BWD_WIN];
   const int b = blockIdx.z, tid = threadIdx.x;
-  const int tx = tid & (DS_T - 1), ty = tid >> 4;
-  const int ox = blockIdx.x * DS_T + tx, oy = blockIdx.y * DS_T + ty;
-  const bool live = ox < a.Wo && oy < a.Ho;
+  const int tx = tid & (DISP_BWD_T - 1), ty = tid >> 4;
+  const int ox = blockIdx.x * DISP_BWD_T + tx, oy = blockIdx.y * DISP_BWD_T + ty;
+  const bool live = ox < g.Wo && oy < g.Ho;
   // window origin: the first coarse cell touched by the tile's first pixel (uniform over the workgroup)
-  const int wy0 = lin_index(min(blockIdx.y * DS_T, a.Ho - 1), a.h, a.Ho, a.sh, 0).i0;
-  const int wx0 = lin_index(min(blockIdx.x * DS_T, a.Wo - 1), a.w, a.Wo, a.sw, 0).i0;
-  for (int dd = tid; dd < a.maxdisp; dd += 256) {
-    const LinIdx lz = lin_index(dd, a.d, a.maxdisp, a.sd, 0);
-    const bool same = lz.i1 == lz.i0;
-    ztab[dd] = make_float4((float)lz.i0, lz.w0, same ? 0.f : lz.w1, same ? lz.w1 : 0.f);
-  }
-  if (tid < 2 * DS_T) {                    // bilinear weights of the tile's columns (tid < 16) / rows onto the window
-    const bool col = tid < DS_T;
-    const int k = tid & (DS_T - 1);
-    const int o = (col ? blockIdx.x : blockIdx.y) * DS_T + k, n_out = col ? a.Wo : a.Ho;
-    const LinIdx l = lin_index(min(o, n_out - 1), col ? a.w : a.h, n_out, col ? a.sw : a.sh, 0);
+  const int wy0 = lin_index(min(blockIdx.y * DISP_BWD_T, g.Ho - 1), g.h, g.Ho, g.sh, 0).i0;
+  const int wx0 = lin_index(min(blockIdx.x * DISP_BWD_T, g.Wo - 1), g.w, g.Wo, g.sw, 0).i0;
+  disp_fill_taps(ztab, g);
+  if (tid < 2 * DISP_BWD_T) {                    // bilinear weights of the tile's columns (tid < 16) / rows onto the window
+    const bool col = tid < DISP_BWD_T;
+    const int k = tid & (DISP_BWD_T - 1);
+    const int o = (col ? blockIdx.x : blockIdx.y) * DISP_BWD_T + k, n_out = col ? g.Wo : g.Ho;
+    const LinIdx l = lin_index(min(o, n_out - 1), col ? g.w : g.h, n_out, col ? g.sw : g.sh, 0);
     const int j0 = l.i0 - (col ? wx0 : wy0), j1 = l.i1 - (col ? wx0 : wy0);
-    for (int j = 0; j < DS_WIN; ++j) {
+    for (int j = 0; j < DISP_BWD_WIN; ++j) {
       const float wv = o < n_out ? (j == j0 ? l.w0 : 0.f) + (j == j1 ? l.w1 : 0.f) : 0.f;
       if (col) wxw[k][j] = wv; else wyw[k][j] = wv;
     }
   }
   __syncthreads();
-  const int hw = a.h * a.w;
-  const float* base = a.cost + (int64_t)b * a.d * hw;
-  float* gbase = a.dcost + (int64_t)b * a.d * hw;
-  const LinIdx ly = lin_index(min(oy, a.Ho - 1), a.h, a.Ho, a.sh, 0);
-  const LinIdx lx = lin_index(min(ox, a.Wo - 1), a.w, a.Wo, a.sw, 0);
-  const int o00 = ly.i0 * a.w + lx.i0, o01 = ly.i0 * a.w + lx.i1, o10 = ly.i1 * a.w + lx.i0, o11 = ly.i1 * a.w + lx.i1;
-  auto plane = [&](int z) -> float {
-    const float* p = base + (int64_t)z * hw;
-    return lerp2(ly.w0, lerp2(lx.w0, p[o00], lx.w1, p[o01]), ly.w1, lerp2(lx.w0, p[o10], lx.w1, p[o11]));
-  };
+  const int hw = g.h * g.w;
+  float* gbase = a.dcost + (int64_t)b * g.d * hw;
+  const DispPlaneSampler<float> smp(a.cost + (int64_t)b * g.d * hw, g, min(oy, g.Ho - 1), min(ox, g.Wo - 1));
   // the pixel's four cotangents; a null plane is a zero plane, and pixels outside the image contribute nothing
-  const int64_t npix = (int64_t)a.Ho * a.Wo, po = (int64_t)oy * a.Wo + ox;
+  const int64_t npix = (int64_t)g.Ho * g.Wo, po = (int64_t)oy * g.Wo + ox;
   const float gmu = live && a.dout ? a.dout[b * npix + po] : 0.f;
   const float gV = live && a.dstats ? a.dstats[((int64_t)b * 3 + 0) * npix + po] : 0.f;
   const float gP = live && a.dstats ? a.dstats[((int64_t)b * 3 + 1) * npix + po] : 0.f;
@@ -73,11 +64,11 @@ __global__ __launch_bounds__(256) void disp_softargmin_stats_bwd_kernel(DispStat
   int kstar = 0;
   {
     int cz = 0;
-    float b0 = plane(0), b1 = plane(a.d > 1 ? 1 : 0);
-    for (int dd = 0; dd < a.maxdisp; ++dd) {
+    float b0 = smp.plane(0), b1 = smp.plane(g.d > 1 ? 1 : 0);
+    for (int dd = 0; dd < g.maxdisp; ++dd) {
       const float4 tb = ztab[dd];
       const int i0 = (int)tb.x;
-      while (i0 > cz) { ++cz; b0 = b1; b1 = plane(cz + 1 < a.d ? cz + 1 : a.d - 1); }
+      while (i0 > cz) { ++cz; b0 = b1; b1 = smp.plane(cz + 1 < g.d ? cz + 1 : g.d - 1); }
       const float t = -fmaf(tb.y + tb.w, b0, tb.z * b1);
       const bool up = t > m;
       const float x = __builtin_amdgcn_exp2f((up ? m - t : t - m) * K);
@@ -101,11 +92,11 @@ __global__ __launch_bounds__(256) void disp_softargmin_stats_bwd_kernel(DispStat
   {
     float blk = 0.f, mid = 0.f, tot = 0.f;
     int cz = 0;
-    float b0 = plane(0), b1 = plane(a.d > 1 ? 1 : 0);
-    for (int dd = 0; dd < a.maxdisp; ++dd) {
+    float b0 = smp.plane(0), b1 = smp.plane(g.d > 1 ? 1 : 0);
+    for (int dd = 0; dd < g.maxdisp; ++dd) {
       const float4 tb = ztab[dd];
       const int i0 = (int)tb.x;
-      while (i0 > cz) { ++cz; b0 = b1; b1 = plane(cz + 1 < a.d ? cz + 1 : a.d - 1); }
+      while (i0 > cz) { ++cz; b0 = b1; b1 = smp.plane(cz + 1 < g.d ? cz + 1 : g.d - 1); }
       const float t = -fmaf(tb.y + tb.w, b0, tb.z * b1);
       const float tm = t - m;
       blk = fmaf(__builtin_amdgcn_exp2f(tm * K), poly(dd, tm, gV, gmu, -gH, gH * ls), blk);
@@ -121,34 +112,34 @@ __global__ __launch_bounds__(256) void disp_softargmin_stats_bwd_kernel(DispStat
   auto flush = [&](int z, float gv) {      // called by EVERY thread at the same point
     pix[tid] = gv;
     __syncthreads();
-    if (tid < DS_T * DS_WIN) {             // (row r, window column j): sum over the row's 16 columns
-      const int r = tid >> 3, j = tid & (DS_WIN - 1);
+    if (tid < DISP_BWD_T * DISP_BWD_WIN) {             // (row r, window column j): sum over the row's 16 columns
+      const int r = tid >> 3, j = tid & (DISP_BWD_WIN - 1);
       float acc = 0.f;
 #pragma unroll
-      for (int c = 0; c < DS_T; ++c) acc = fmaf(wxw[c][j], pix[r * DS_T + c], acc);
+      for (int c = 0; c < DISP_BWD_T; ++c) acc = fmaf(wxw[c][j], pix[r * DISP_BWD_T + c], acc);
       colsum[r][j] = acc;
     }
     __syncthreads();
-    if (tid < DS_WIN * DS_WIN) {           // (window row jy, window column jx): sum over the 16 rows
-      const int jy = tid >> 3, jx = tid & (DS_WIN - 1);
+    if (tid < DISP_BWD_WIN * DISP_BWD_WIN) {           // (window row jy, window column jx): sum over the 16 rows
+      const int jy = tid >> 3, jx = tid & (DISP_BWD_WIN - 1);
       float acc = 0.f;
 #pragma unroll
-      for (int r = 0; r < DS_T; ++r) acc = fmaf(wyw[r][jy], colsum[r][jx], acc);
+      for (int r = 0; r < DISP_BWD_T; ++r) acc = fmaf(wyw[r][jy], colsum[r][jx], acc);
       const int cx = wx0 + jx, cy = wy0 + jy;
-      if (acc != 0.f && cx < a.w && cy < a.h) atomicAdd(gbase + (int64_t)z * hw + cy * a.w + cx, acc);
+      if (acc != 0.f && cx < g.w && cy < g.h) atomicAdd(gbase + (int64_t)z * hw + cy * g.w + cx, acc);
     }
     // (the next flush writes pix only after its own barrier-separated readers are done, as in the plain adjoint)
   };
   // pass 2: walk the fine samples again; a0 / a1 collect the gradient of coarse planes cz / cz+1
   int cz = 0;
-  float b0 = plane(0), b1 = plane(a.d > 1 ? 1 : 0);
+  float b0 = smp.plane(0), b1 = smp.plane(g.d > 1 ? 1 : 0);
   float a0 = 0.f, a1 = 0.f;
-  for (int dd = 0; dd < a.maxdisp; ++dd) {
+  for (int dd = 0; dd < g.maxdisp; ++dd) {
     const float4 tb = ztab[dd];
     const int i0 = (int)tb.x;
     while (i0 > cz) {                      // wave- and workgroup-uniform: the table is the same for every pixel
       flush(cz, a0); a0 = a1; a1 = 0.f;
-      ++cz; b0 = b1; b1 = plane(cz + 1 < a.d ? cz + 1 : a.d - 1);
+      ++cz; b0 = b1; b1 = smp.plane(cz + 1 < g.d ? cz + 1 : g.d - 1);
     }
     const float t = -fmaf(tb.y + tb.w, b0, tb.z * b1);
     const float tm = t - m;
@@ -157,7 +148,7 @@ __global__ __launch_bounds__(256) void disp_softargmin_stats_bwd_kernel(DispStat
     a1 = fmaf(gv, tb.z, a1);
   }
   flush(cz, a0);
-  if (cz + 1 < a.d) flush(cz + 1, a1);
+  if (cz + 1 < g.d) flush(cz + 1, a1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -261,15 +252,14 @@ extern "C" int ragmi_disp_softargmin_stats_bwd(const void* cost, const void* dou
   RAGMI_REQUIRE(dout || dstats, RAGMI_EINVAL, "disp_softargmin_stats_bwd: both cotangents are null");
   RAGMI_REQUIRE(B > 0 && d > 0 && h > 0 && w > 0 && maxdisp > 0 && Ho > 0 && Wo > 0 && B <= 65535, RAGMI_EINVAL,
                 "disp_softargmin_stats_bwd: bad size");
-  // the coarse window of a 16 x 16 fine tile must fit DS_WIN cells per axis: holds for the x3 upsample of Disp (16/3 + 2 taps <= 8)
+  // the coarse window of a 16 x 16 fine tile must fit DISP_BWD_WIN cells per axis: holds for the x3 upsample of Disp (16/3 + 2 taps <= 8)
   RAGMI_REQUIRE(Ho == 3 * h && Wo == 3 * w, RAGMI_EUNSUPPORTED,
                 "disp_softargmin_stats_bwd: built for the x3 upsample of Disp (Ho = 3h, Wo = 3w)");
   RAGMI_REQUIRE((int64_t)h * w < (1ll << 30), RAGMI_EUNSUPPORTED, "disp_softargmin_stats_bwd: size too large");
   const size_t lds = (size_t)maxdisp * sizeof(float4);
   RAGMI_REQUIRE(lds <= 48 * 1024, RAGMI_EUNSUPPORTED, "disp_softargmin_stats_bwd: maxdisp = %d exceeds the tap table (3072)", maxdisp);
-  DispStatsBwdArgs a{(const float*)cost, (const float*)dout, (const float*)dstats, (float*)dcost, d, h, w, maxdisp, Ho, Wo,
-                     lin_scale(d, maxdisp, 0), lin_scale(h, Ho, 0), lin_scale(w, Wo, 0)};
-  hipLaunchKernelGGL(disp_softargmin_stats_bwd_kernel, dim3((unsigned)ceil_div(Wo, DS_T), (unsigned)ceil_div(Ho, DS_T), B), dim3(256), lds,
+  DispStatsBwdArgs a{(const float*)cost, (const float*)dout, (const float*)dstats, (float*)dcost, disp_geom(d, h, w, maxdisp, Ho, Wo)};
+  hipLaunchKernelGGL(disp_softargmin_stats_bwd_kernel, dim3((unsigned)ceil_div(Wo, DISP_BWD_T), (unsigned)ceil_div(Ho, DISP_BWD_T), B), dim3(256), lds,
                      static_cast<hipStream_t>(stream), a);
   return check_launch("disp_softargmin_stats_bwd");
 }

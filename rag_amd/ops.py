@@ -868,13 +868,19 @@ def add(a: torch.Tensor, a_ch0: int, b: torch.Tensor, b_ch0: int, out: torch.Ten
     return out
 
 
+def _single_channel(what: str, cost: torch.Tensor) -> torch.Tensor:
+    """cost[B,1,d,h,w] -> [B,d,h,w]; a [B,d,h,w] volume passes through."""
+    if cost.dim() == 5:
+        if cost.shape[1] != 1:
+            raise ValueError(f"{what}: expected a single-channel cost volume")
+        cost = cost[:, 0]
+    return cost
+
+
 def disp_softargmin(cost: torch.Tensor, maxdisp: int) -> torch.Tensor:
     """Fused Disp.forward: cost[B,1,d,h,w] (or [B,d,h,w]) -> disparity [B,3h,3w]."""
     dt = _act(cost)
-    if cost.dim() == 5:
-        if cost.shape[1] != 1:
-            raise ValueError("disp_softargmin: expected a single-channel cost volume")
-        cost = cost[:, 0]
+    cost = _single_channel("disp_softargmin", cost)
     cost = cost.contiguous()
     B, d, h, w = cost.shape
     out = torch.empty((B, 3 * h, 3 * w), device=cost.device, dtype=torch.float32)
@@ -915,10 +921,7 @@ def disp_softargmin_stats(cost: torch.Tensor, maxdisp: int, out: Optional[torch.
     """disp_softargmin with the per-pixel statistics of the softmin distribution, one launch: cost[B,1,d,h,w] (or [B,d,h,w]) ->
     (disparity [B,3h,3w] - the bits of disp_softargmin, stats [B,3,3h,3w] = variance px^2, peak, entropy nats).  Inference only."""
     dt = _act(cost)
-    if cost.dim() == 5:
-        if cost.shape[1] != 1:
-            raise ValueError("disp_softargmin_stats: expected a single-channel cost volume")
-        cost = cost[:, 0]
+    cost = _single_channel("disp_softargmin_stats", cost)
     cost = cost.contiguous()
     B, d, h, w = cost.shape
     out, stats = _stats_outputs("disp_softargmin_stats", cost, B, 3 * h, 3 * w, out, stats)
@@ -967,10 +970,7 @@ def disp_softargmin_mode(cost: torch.Tensor, maxdisp: int, radius: int, out: Opt
     """disp_softargmin_stats with the mode-local disparity, one launch: cost[B,1,d,h,w] (or [B,d,h,w]) -> (disparity [B,3h,3w] and stats
     [B,3,3h,3w], the bits of disp_softargmin_stats, mode [B,3,3h,3w] = index k* of the smallest upsampled cost, disparity regressed over
     |k - k*| <= radius about k*, probability mass of that window).  Inference only."""
-    if cost.dim() == 5:
-        if cost.shape[1] != 1:
-            raise ValueError("disp_softargmin_mode: expected a single-channel cost volume")
-        cost = cost[:, 0]
+    cost = _single_channel("disp_softargmin_mode", cost)
     B, d, h, w = cost.shape
     radius = _mode_check("disp_softargmin_mode", B, 3 * h, 3 * w, maxdisp, radius, mode)
     dt = _act(cost)

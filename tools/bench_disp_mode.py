@@ -1,8 +1,8 @@
 """The disparity head's plain, statistics and mode launches (rag_amd/csrc/disp.hip) at the headline head shape, cost [1, 1, 64, 128, 416]
 -> 384 x 1248, fp32 cost.  One process; writes one JSON file (default profiles/disp_mode_bench.json) and prints it.
-  * plain_us      ops.disp_softargmin       (disp_softargmin_x3_kernel<float>, the register form);
-  * stats_us      ops.disp_softargmin_stats (disp_softargmin_x3_stats_kernel<float>), caller-owned outputs;
-  * mode_us       ops.disp_softargmin_mode  (disp_softargmin_x3_mode_kernel<float>) at radius MODE_RADIUS, caller-owned outputs, and
+  * plain_us      ops.disp_softargmin       (disp_softargmin_x3_kernel<float, false, false>, the register form);
+  * stats_us      ops.disp_softargmin_stats (disp_softargmin_x3_kernel<float, true, false>), caller-owned outputs;
+  * mode_us       ops.disp_softargmin_mode  (disp_softargmin_x3_kernel<float, true, true>) at radius MODE_RADIUS, caller-owned outputs, and
                   mode_full_us at radius maxdisp (the radius is a kernel argument: the same code object);
                   all: device events around replays of a captured graph that holds INNER launches, the graphs replayed ALTERNATELY over
                   ROUNDS rounds, median of the rounds (the spread is reported);

@@ -1,8 +1,8 @@
 """The disparity head with and without the per-pixel statistics of its distribution (rag_amd/csrc/disp.hip) at the headline head shape,
 cost [B, 1, 64, 128, 416] -> 384 x 1248, B = 1 and 8, fp32 cost.  One process; writes one JSON file (default
 profiles/disp_stats_bench.json) and prints it.  Per batch size:
-  * plain_us      ops.disp_softargmin       (disp_softargmin_x3_kernel<float>, the register form);
-  * stats_us      ops.disp_softargmin_stats (disp_softargmin_x3_stats_kernel<float>), caller-owned outputs;
+  * plain_us      ops.disp_softargmin       (disp_softargmin_x3_kernel<float, false, false>, the register form);
+  * stats_us      ops.disp_softargmin_stats (disp_softargmin_x3_kernel<float, true, false>), caller-owned outputs;
                   both: device events around replays of a captured graph that holds INNER launches, the two graphs replayed
                   ALTERNATELY over ROUNDS rounds, median of the rounds (the spread is reported);
   * aten_us       the twin rag_amd.metrics.disp_stats_torch on the same GPU (F.interpolate -> softmin -> moments), device events

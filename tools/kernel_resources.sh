@@ -1,8 +1,11 @@
 #!/bin/bash
 # Register / spill / occupancy summary of every kernel of one source file (hipcc -Rpass-analysis=kernel-resource-usage):
-#   bash tools/kernel_resources.sh rag_amd/csrc/conv3d_x3.hip [name filter regex]
-src=$1; filt=${2:-.}
-/opt/rocm/bin/hipcc -O3 -std=c++20 --offload-arch=gfx950 -Iinclude -Irag_amd/csrc -Rpass-analysis=kernel-resource-usage -c "$src" -o /dev/null 2>&1 |
+#   bash tools/kernel_resources.sh rag_amd/csrc/conv3d_x3.hip [name filter regex] [extra hipcc flags ...]
+# The Makefile's per-file flags (its "Per-file code generation choices" block: keep the list below in step with it) are applied, so
+# the figures are those of the build that ships.
+src=$1; filt=${2:-.}; shift $(( $# < 2 ? $# : 2 ))
+case $(basename "$src") in disp.hip|conv3d_c1.hip) set -- -fno-slp-vectorize "$@";; esac
+/opt/rocm/bin/hipcc -O3 -std=c++20 --offload-arch=gfx950 -Iinclude -Irag_amd/csrc "$@" -Rpass-analysis=kernel-resource-usage -c "$src" -o /dev/null 2>&1 |
   python3 -c "
 import re,sys,subprocess
 cur={}
