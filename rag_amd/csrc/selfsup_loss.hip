@@ -89,6 +89,7 @@ __device__ __forceinline__ float edge_weight(const float* __restrict__ lb, int64
 template <int C, bool GRAD>
 __device__ __forceinline__ float smooth_px(const float* __restrict__ lb, const float* __restrict__ db, int64_t hw, int H, int W, int y,
                                            int x, float d, float& gsum) {
+#pragma clang fp contract(off)                                          // the same rounding with and without GRAD, as the SSIM term
   const int64_t i = (int64_t)y * W + x;
   float f = 0.f;
   if (x < W - 1) {
@@ -142,17 +143,24 @@ __global__ __launch_bounds__(SS_WG) void selfsup_loss_kernel(SelfSupArgs a, doub
     constexpr float C1 = 1e-4f, C2 = 9e-4f;                              // 0.01**2, 0.03**2 (loss.py:84-85)
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-      float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
+      float mx, my, A, Bn, Cd, D, S, h;
+      {
+        // The term's value, without contraction: which products the compiler fuses into a following sum depends on what else uses
+        // them, so the GRAD and the terms-only instantiation would otherwise round the same block differently (seen as one ulp of
+        // the SSIM mean).  Unfused is also the reference's arithmetic: avg_pool2d, products and sums are separate ATen kernels.
+#pragma clang fp contract(off)
+        float sx = 0.f, sy = 0.f, sxx = 0.f, syy = 0.f, sxy = 0.f;
 #pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const float x = lv[k][c], y = ev[k][c];
-        sx += x; sy += y; sxx += x * x; syy += y * y; sxy += x * y;
+        for (int k = 0; k < 9; ++k) {
+          const float x = lv[k][c], y = ev[k][c];
+          sx += x; sy += y; sxx += x * x; syy += y * y; sxy += x * y;
+        }
+        mx = sx / 9.f; my = sy / 9.f;
+        const float vx = sxx / 9.f - mx * mx, vy = syy / 9.f - my * my, vxy = sxy / 9.f - mx * my;
+        A = 2.f * mx * my + C1; Bn = 2.f * vxy + C2; Cd = mx * mx + my * my + C1; D = vx + vy + C2;
+        S = (A * Bn) / (Cd * D);
+        h = (1.f - S) / 2.f;
       }
-      const float mx = sx / 9.f, my = sy / 9.f;
-      const float vx = sxx / 9.f - mx * mx, vy = syy / 9.f - my * my, vxy = sxy / 9.f - mx * my;
-      const float A = 2.f * mx * my + C1, Bn = 2.f * vxy + C2, Cd = mx * mx + my * my + C1, D = vx + vy + C2;
-      const float S = (A * Bn) / (Cd * D);
-      const float h = (1.f - S) / 2.f;
       acc_ssim += fminf(fmaxf(h, 0.f), 1.f);
       if (GRAD) {
         // d term / d y_i = -1/2 dS/dy_i (clamp passes the gradient on the closed interval), with

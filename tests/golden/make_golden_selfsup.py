@@ -19,6 +19,11 @@ Fixtures:
                               seed 61, asserted equal to g6's ``sd::`` entries, which the tests load from g6) with re_and_sm_loss
                               instead of smooth-L1, on smooth images (noise upsampled x4, bilinear).  Keys as g6 (without the
                               ``sd::`` copy) plus ``grad::disp``.
+  g14_selfsup_edges.npz       the edge table G14_ROWS (B, C, H, W, d_lo, d_hi) of the loss alone, keys as g12: every channel count,
+                              every (H % 3, W % 3), one block per row / column, 63 / 64 / 65 threads, a workgroup boundary inside
+                              a later batch item, disparities of both signs, and three rows again with the disparity constant on
+                              4 x 4 tiles.  Disparities are redrawn until ``ill_conditioned`` marks no pixel (asserted); ``probes``
+                              holds the pixels tests/test_selfsup_sweep.py moves on PROBE_ROW.
 
 Usage:  python tests/golden/make_golden_selfsup.py
 """
@@ -74,29 +79,127 @@ def near_kink(disp32, W):
     return (np.abs(a - np.round(a)) < EPS_XS) | (np.abs(b - np.round(b)) < EPS_XS)
 
 
-def draw_disp(gen, B, H, W, dmax, tile=None):
-    """U(0, dmax) disparities (constant on tile x tile squares if `tile`), redrawn until no xs is within EPS_XS of an integer."""
+def draw_disp_rounds(gen, B, H, W, dmax, tile=None, dmin=0.0, bad_of=None, rounds=100):
+    """U(dmin, dmax) disparities (constant on tile x tile squares if `tile`), redrawn where `bad_of(d)` (default: near_kink) marks a
+    pixel, for at most `rounds` rounds.  Returns (disparities, redraw rounds used)."""
+    if bad_of is None:
+        bad_of = lambda d: near_kink(d, W)  # noqa: E731
+
+    def uniform(shape):
+        return (torch.rand(shape, generator=gen) * (dmax - dmin) + dmin).numpy()
+
+    used = 0
     if tile is None:
-        d = (torch.rand((B, H, W), generator=gen) * dmax).numpy()
-        for _ in range(100):
-            bad = near_kink(d, W)
-            if not bad.any():
+        d = uniform((B, H, W))
+        for used in range(rounds + 1):
+            bad = bad_of(d)
+            if not bad.any() or used == rounds:
                 break
-            d[bad] = (torch.rand((int(bad.sum()),), generator=gen) * dmax).numpy()
+            d[bad] = uniform((int(bad.sum()),))
     else:
         th, tw = -(-H // tile), -(-W // tile)
-        t = (torch.rand((B, th, tw), generator=gen) * dmax).numpy()
-        for _ in range(100):
+        t = uniform((B, th, tw))
+        for used in range(rounds + 1):
             d = np.repeat(np.repeat(t, tile, axis=1), tile, axis=2)[:, :H, :W].copy()
-            bad = near_kink(d, W)
-            if not bad.any():
+            bad = bad_of(d)
+            if not bad.any() or used == rounds:
                 break
             bt = np.zeros(t.shape, dtype=bool)
             for b, y, x in zip(*np.nonzero(bad)):
                 bt[b, y // tile, x // tile] = True
-            t[bt] = (torch.rand((int(bt.sum()),), generator=gen) * dmax).numpy()
-    assert not near_kink(d, W).any(), "could not keep every xs away from the bilinear kinks"
-    return d.astype(np.float32)
+            t[bt] = uniform((int(bt.sum()),))
+    assert not bad_of(d).any(), "could not draw disparities that meet the conditioning rules"
+    return d.astype(np.float32), used
+
+
+def draw_disp(gen, B, H, W, dmax, tile=None):
+    """U(0, dmax) disparities (constant on tile x tile squares if `tile`), redrawn until no xs is within EPS_XS of an integer."""
+    return draw_disp_rounds(gen, B, H, W, dmax, tile)[0]
+
+
+# ---- G14: the edge table of tests/test_selfsup_sweep.py.  (B, C, H, W, d_lo, d_hi); seed 700 + position (tiled rows follow the table)
+G14_ROWS = (
+    (1, 3, 3, 3, -0.5, 1.5),                                                   # one thread, Hb = Wb = 1, no remainder
+    (1, 1, 4, 5, -1.0, 3.0),                                                   # C = 1, Hb = Wb = 1, remainder 1 row / 2 columns
+    (2, 2, 5, 4, -1.0, 3.0),                                                   # C = 2, Hb = Wb = 1, remainder 2 rows / 1 column, B = 2
+    (1, 4, 6, 9, -2.0, 6.0),                                                   # C = 4, no remainder
+    (1, 1, 3, 7, -2.0, 5.0),                                                   # Hb = 1, Wb = 2
+    (1, 2, 8, 3, -1.0, 2.0),                                                   # Wb = 1, Hb = 2
+) + tuple((1, 3, H, W, -3.0, 9.0) for H in (6, 7, 8) for W in (9, 10, 11)) + (  # all nine (H % 3, W % 3) with Hb, Wb >= 2
+    (1, 3, 21, 27, -6.0, 20.0),                                                # 63 threads
+    (1, 3, 24, 24, -6.0, 20.0),                                                # 64 threads
+    (1, 1, 17, 41, -8.0, 30.0),                                                # 65 threads: a second workgroup with one live lane
+    (3, 3, 16, 17, -4.0, 24.0),                                                # 75 threads: the workgroup boundary inside batch item 2
+    (2, 4, 13, 22, -20.0, 44.0),                                               # C = 4, most disparities out of view on both sides
+    (1, 3, 23, 29, -4.0, 12.0),                                                # 63 threads with remainder 2 / 2
+)
+G14_TILED = ((1, 3, 7, 10, -3.0, 9.0), (3, 3, 16, 17, -4.0, 24.0), (2, 4, 13, 22, -20.0, 44.0))   # disparity constant on 4 x 4 tiles
+G14_TILE = 4
+PROBE_ROW = (1, 3, 8, 11, -3.0, 9.0)
+PROBES = ((4, 5), (6, 4), (3, 9))          # (y, x) on PROBE_ROW: inside a 3x3 block, in the remainder rows, in the remainder columns
+PROBE_SHIFT = 0.37
+EPS_COND = 1e-3
+MIN_SHARE = 0.25
+
+
+def g14_cases():
+    """[(tag, row, tile or None)] in fixture order."""
+    tag = "B{}C{}_{}x{}".format
+    return [(tag(*r[:4]), r, None) for r in G14_ROWS] + [(tag(*r[:4]) + "_tiled", r, G14_TILE) for r in G14_TILED]
+
+
+def selfsup_parts64(left, right, disp):
+    """The loss's intermediate values in fp64, from arrays: (left_est [B,C,H,W], kept-by-the-mask [B,H,W], (1 - SSIM)/2 per 3x3 block
+    and channel before the clamp [B,C,Hb,Wb]).  Plain torch, so that the rules below can be checked without the reference."""
+    lt, rt = torch.from_numpy(np.asarray(left)).double(), torch.from_numpy(np.asarray(right)).double()
+    d = torch.from_numpy(np.asarray(disp)).double()
+    B, _, H, W = lt.shape
+    xs = torch.arange(W, dtype=torch.float64).view(1, 1, W) - d
+    ys = torch.arange(H, dtype=torch.float64).view(1, H, 1).expand(B, H, W)
+    grid = torch.stack((2 * xs / (W - 1) - 1, 2 * ys / (H - 1) - 1), dim=-1)
+    kept = F.grid_sample(torch.ones_like(rt[:, :1]), grid, mode="bilinear", padding_mode="zeros", align_corners=False)[:, 0] >= 0.9999
+    est = F.grid_sample(rt, grid, mode="bilinear", padding_mode="zeros", align_corners=False) * kept[:, None]
+    mu_x, mu_y = F.avg_pool2d(lt, 3), F.avg_pool2d(est, 3)
+    var_x, var_y = F.avg_pool2d(lt * lt, 3) - mu_x * mu_x, F.avg_pool2d(est * est, 3) - mu_y * mu_y
+    cov = F.avg_pool2d(lt * est, 3) - mu_x * mu_y
+    ssim = (2 * mu_x * mu_y + 1e-4) * (2 * cov + 9e-4) / ((mu_x * mu_x + mu_y * mu_y + 1e-4) * (var_x + var_y + 9e-4))
+    return est, kept, (1 - ssim) / 2
+
+
+def ill_conditioned(left, right, disp):
+    """Pixels [B,H,W] on or next to one of the loss's kinks, where an fp32 and an fp64 evaluation may legitimately take different
+    sides: (1) sample abscissa within EPS_XS of an integer (near_kink); (2) kept by the mask and |left - left_est| < EPS_COND in some
+    channel; (3) in a 3x3 block whose (1 - SSIM)/2 lies within EPS_COND of 0 or 1 in some channel (the clamp); (4) a neighbour's
+    disparity differs by less than EPS_COND without being equal (the smoothness term's |.|).  And (5), so that no row degenerates
+    into smoothness only: at H >= 6, W >= 9 the mask keeps at least MIN_SHARE of the pixels, else the out-of-view ones are marked."""
+    disp = np.asarray(disp, dtype=np.float32)
+    lt = torch.from_numpy(np.asarray(left)).double()
+    H, W = disp.shape[1:]
+    bad = near_kink(disp, W)
+    est, kept, half = selfsup_parts64(left, right, disp)
+    bad |= (kept & ((lt - est).abs() < EPS_COND).any(1)).numpy()
+    blocks = ((half.abs() < EPS_COND) | ((half - 1).abs() < EPS_COND)).any(1).numpy()
+    bad[:, :3 * (H // 3), :3 * (W // 3)] |= np.repeat(np.repeat(blocks, 3, axis=1), 3, axis=2)
+    d64 = disp.astype(np.float64)
+    for a, b in ((np.s_[:, :, :-1], np.s_[:, :, 1:]), (np.s_[:, :-1, :], np.s_[:, 1:, :])):
+        gap = np.abs(d64[a] - d64[b])
+        close = (gap < EPS_COND) & (gap != 0)
+        bad[a] |= close
+        bad[b] |= close
+    if H >= 6 and W >= 9 and float(kept.double().mean()) < MIN_SHARE:      # (5): out-of-view pixels off the always-masked rows 0, H-1
+        bad[:, 1:H - 1] |= ~kept.numpy()[:, 1:H - 1]
+    return bad
+
+
+def unmasked_share(left, right, disp):
+    return float(selfsup_parts64(left, right, disp)[1].double().mean())
+
+
+def probe_disp(disp, probe):
+    """PROBE_ROW's disparities with the one at `probe` moved by PROBE_SHIFT."""
+    moved = np.array(disp, dtype=np.float32, copy=True)
+    moved[0, probe[0], probe[1]] += np.float32(PROBE_SHIFT)
+    return moved
 
 
 def run_loss(loss_mod, disp, left, right, dtype):
@@ -150,6 +253,43 @@ def main():
         print(f"  {tag}: loss {l64:.6f} terms {t64} |fp32-fp64| grad {np.abs(g32 - g64).max():.2e}")
     arrays["cases"] = np.array(list(cases))
     save("g12_selfsup_loss", **arrays)
+
+    # ---- G14: the loss alone on the edge table
+    arrays, redrawn = {}, []
+    for i, (tag, (B, C, H, W, lo, hi), tile) in enumerate(g14_cases()):
+        gen = torch.Generator().manual_seed(700 + i)
+        left = torch.randn((B, C, H, W), generator=gen).numpy()
+        right = torch.randn((B, C, H, W), generator=gen).numpy()
+        disp, rounds = draw_disp_rounds(gen, B, H, W, hi, tile, dmin=lo, bad_of=lambda d: ill_conditioned(left, right, d), rounds=200)
+        if rounds:
+            redrawn.append((tag, rounds))
+        assert not ill_conditioned(left, right, disp).any() and float(disp.min()) >= lo and float(disp.max()) <= hi
+        share = unmasked_share(left, right, disp)
+        assert share > 0 and (share >= MIN_SHARE or H < 6 or W < 9), (tag, share)
+        if tile:
+            assert (disp[:, :, :-1] == disp[:, :, 1:]).mean() > 0.5
+        if (B, C, H, W, lo, hi) == PROBE_ROW:
+            for probe in PROBES:               # the locality test's shifted inputs stay clear of every kink too
+                assert not ill_conditioned(left, right, probe_disp(disp, probe)).any(), probe
+        torch.set_default_dtype(torch.float64)                 # the rules were checked on the reference's own left_est
+        try:
+            with torch.no_grad():
+                est_ref = loss_mod.warp(torch.from_numpy(right).double(), torch.from_numpy(disp).double().unsqueeze(1))
+        finally:
+            torch.set_default_dtype(torch.float32)
+        assert float((est_ref - selfsup_parts64(left, right, disp)[0]).abs().max()) <= 1e-12
+        l32, t32, g32 = run_loss(loss_mod, disp, left, right, torch.float32)
+        l64, t64, g64 = run_loss(loss_mod, disp, left, right, torch.float64)
+        yard = np.abs(g32 - g64).max() / np.abs(g64).max()
+        assert yard <= 2.5e-4, (tag, yard)     # the reference's own fp32 run is a usable yardstick: else redraw the row
+        arrays.update({f"{tag}::left": left, f"{tag}::right": right, f"{tag}::disp": disp,
+                       f"{tag}::loss32": l32, f"{tag}::terms32": t32, f"{tag}::grad32": g32,
+                       f"{tag}::loss64": l64, f"{tag}::terms64": t64, f"{tag}::grad64": g64})
+        print(f"  {tag}: loss {l64:.6f} unmasked {share:.2f} redraw rounds {rounds} |fp32-fp64| grad / max|g| {yard:.2e}")
+    arrays["cases"] = np.array([tag for tag, _row, _tile in g14_cases()])
+    arrays["probes"] = np.array(PROBES, dtype=np.int64)
+    print(f"  g14 rows redrawn: {redrawn}")
+    save("g14_selfsup_edges", **arrays)
 
     # ---- G13: g6's training step with the self-supervised loss
     rows = np.array([[0, 1], [1, 1], [2, 1], [3, 1], [5, 1], [6, 1]])
