@@ -698,6 +698,33 @@ int ragmi_masked_smooth_l1_bwd(const void* disp_est, const void* disp_gt, const 
                                int B, int H, int W, float maxdisp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Sparsification curves of a per-pixel uncertainty and their areas (AUSE, AURG), per image, in one device pass without a sort
+ * (no counterpart in the reference, which has no uncertainty).  disp, unc, gt: [B,H,W] fp32; larger unc = less certain.
+ *   mask   0 < gt < maxdisp and disp, unc finite; N = masked pixels of the image
+ *   e_q    rint(|double(disp) - double(gt)| 2^20), an integer (saturating at 2^32 - 1, i.e. 4096 px); every error sum is an integer sum
+ *   bad    E > 3 && E / |gt| > 0.05 with E = |gt - disp| in fp32 (D1's flag of ragmi_stereo_metrics_fwd)
+ *   cuts   j = 0..K-1: r_j = (j N) / K removed, n_j = N - r_j kept
+ *   S_x[j] over the n_j pixels of smallest unc (total order on the values, -0 == +0); a group of c pixels of equal unc of which the cut
+ *          keeps m contributes double(group sum) * double(m) / double(c), so no tie order enters:
+ *          S_epe[j] = float((double(sum below) + share) 2^-20 / double(n_j)), S_d1[j] likewise over the bad counts
+ *   O_epe[j] the same with e_q as the key;  O_d1[j] = max(0, Nbad - r_j) / n_j
+ *   AUSE_x = mean_j(S_x[j] - O_x[j]),  AURG_x = mean_j(S_x[0] - S_x[j]), in double over the stored floats, j ascending
+ * curves: [B,4,K] fp32 = S_epe, O_epe, S_d1, O_d1;  scalars: [B,6] fp32 = AUSE_epe, AURG_epe, AUSE_d1, AURG_d1, N, Nbad.  An image with
+ * N = 0 gets NaN in its curves and its four areas (N = Nbad = 0 are stored) and is not added to the meter.
+ * meter (may be NULL): double [4K + 7], 8-byte aligned, zeroed by the caller at the start of an epoch: a last one-workgroup launch adds
+ * the counted images' 4K curve floats and 6 scalars in double, images in order, one thread per column, and their number to meter[4K + 6].
+ * workspace: 16-byte aligned, ragmi_sparsification_workspace_elems(B,H,W,K) elements of 16 bytes =
+ *   2 B (2048 + 3 K 128)      histogram bins {u32 count, u32 bad, u64 sum e_q} of the 11 / 7 / 7 / 7-bit radix levels, two keys
+ *   + 2 B (4 * 32 * 3 + 1)    cut records of the four levels and {N, Nbad}
+ * (0 for sizes the call refuses; independent of H and W; 2.5 MB at B = 8, K = 20); cleared on the stream by the call's first kernel.
+ * Ten launches (eleven with a meter), kernels only (no memset / memcpy node); 64-bit integer atomics only, so bitwise reproducible;
+ * no allocation, no host synchronisation.  RAGMI_EINVAL before any launch: a null disp / unc / gt / workspace / curves / scalars,
+ * B, H, W <= 0 or B > 65535, K outside 1..32, H * W >= 2^31, maxdisp <= 0, a workspace not 16-byte or a meter not 8-byte aligned. */
+int64_t ragmi_sparsification_workspace_elems(int B, int H, int W, int K);
+int ragmi_sparsification_fwd(const void* disp, const void* unc, const void* gt, int B, int H, int W, float maxdisp, int K,
+                             void* workspace, void* curves, void* scalars, void* meter, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Self-supervised loss of the continual-adaptation mode (src_self/approaches/rag.py:266-278, supervise=False):
  * re_and_sm_loss(disp, left, right) of src_self/models/loss.py:112-141 and its gradient with respect to disp.
  *   left_est[c] = m * bilinear(right[c], xs, ys), xs = ((2 (x - d)/(W-1) - 1 + 1) W - 1)/2, ys = ((2 y/(H-1) - 1 + 1) H - 1)/2

@@ -196,6 +196,9 @@ SIGNATURES = {
                                            c_void_p]),
     "ragmi_uncertainty_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                            c_float, c_float, c_void_p]),
+    "ragmi_sparsification_workspace_elems": (c_int64, [c_int, c_int, c_int, c_int]),
+    "ragmi_sparsification_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
 }
 
 

@@ -113,6 +113,23 @@ class DispStats:
     def entropy(self) -> torch.Tensor:
         return self.tensor[:, 2]
 
+    def _uncertainty(self, which: str) -> torch.Tensor:
+        if which == "variance":
+            return self.variance
+        if which == "entropy":
+            return self.entropy
+        if which == "one_minus_peak":
+            return 1.0 - self.peak
+        if which == "one_minus_mode_mass":
+            raise ValueError("sparsification: which='one_minus_mode_mass' needs a DispMode (a forward_mode result); this is a DispStats")
+        raise ValueError(f"sparsification: which must be one of {SPARSIFY_WHICH}, got {which!r}")
+
+    def sparsification(self, gt: torch.Tensor, which: str = "variance", meter: Optional["CalibrationMeter"] = None,
+                       maxdisp: float = 192, fractions: int = 20) -> "Sparsification":
+        """Sparsification curves of `.disp` against gt [B,H,W] with one of the head's own statistics as the uncertainty: `which` in
+        "variance", "entropy", "one_minus_peak", and on a DispMode "one_minus_mode_mass".  See `sparsification`."""
+        return sparsification(self.disp, self._uncertainty(which), gt, maxdisp, fractions, meter)
+
 
 def refuse_autograd(what: str, *ts) -> None:
     """The statistics launches have no backward: refuse an input that autograd would track."""
@@ -179,6 +196,11 @@ class DispMode(DispStats):
     @property
     def mode_mass(self) -> torch.Tensor:
         return self.mode_tensor[:, 2]
+
+    def _uncertainty(self, which: str) -> torch.Tensor:
+        if which == "one_minus_mode_mass":
+            return 1.0 - self.mode_mass
+        return super()._uncertainty(which)
 
 
 def _window_torch(p: torch.Tensor, radius: int, index: torch.Tensor) -> torch.Tensor:
@@ -326,6 +348,190 @@ def uncertainty_loss(disp: torch.Tensor, stats: torch.Tensor, gt: torch.Tensor, 
     if not disp.is_cuda:
         return uncertainty_loss_torch(disp, stats, gt, maxdisp, var_floor)
     return UncertaintyLossFn.apply(disp, stats, gt, maxdisp, var_floor)
+
+
+# --------------------------------------------------------------------------- scoring the uncertainty: sparsification curves, AUSE, AURG
+SPARSIFY_WHICH = ("variance", "entropy", "one_minus_peak", "one_minus_mode_mass")
+CURVE_NAMES = ("S_epe", "O_epe", "S_d1", "O_d1")
+SCALAR_NAMES = ("AUSE_epe", "AURG_epe", "AUSE_d1", "AURG_d1", "N", "Nbad")
+MAX_FRACTIONS = 32
+_EQ_MAX = 4294967295.0     # e_q saturates at 2^32 - 1 (4096 px): it is the 32-bit radix key of the error-ranked curve O
+
+
+def _fractions(fractions) -> int:
+    if int(fractions) != fractions or not 1 <= int(fractions) <= MAX_FRACTIONS:
+        raise ValueError(f"sparsification: fractions must be an integer in 1..{MAX_FRACTIONS}, got {fractions!r}")
+    return int(fractions)
+
+
+class CalibrationMeter:
+    """Running float64 sums of the per-image sparsification rows of an epoch, on the device: `sums` [4K + 7] = the four curves, the
+    six scalars, the number of images counted (those with a non-empty mask).  `sparsification(..., meter=m)` adds a batch in its
+    finalize kernel (no extra launch, nothing leaves the device); `mean()` is the epoch's one device-to-host copy."""
+
+    def __init__(self, device, fractions: int = 20):
+        self.fractions = _fractions(fractions)
+        self.sums = torch.zeros((4 * self.fractions + 7,), device=device, dtype=torch.float64)
+
+    def reset(self) -> None:
+        self.sums.zero_()
+
+    def mean(self) -> Dict[str, object]:
+        """CURVE_NAMES -> list of K floats, SCALAR_NAMES -> float (each the mean over the counted images; nan before the first one),
+        "images" -> the number counted."""
+        vals = self.sums.tolist()          # the only synchronisation
+        K, n = self.fractions, vals[-1]
+        avg = [v / n if n else float("nan") for v in vals[:-1]]
+        out: Dict[str, object] = {name: avg[c * K:(c + 1) * K] for c, name in enumerate(CURVE_NAMES)}
+        out.update(zip(SCALAR_NAMES, avg[4 * K:]))
+        out["images"] = n
+        return out
+
+
+class Sparsification:
+    """Result of `sparsification`: `.tensor` [B,4,K] fp32 holds S_epe, O_epe, S_d1, O_d1 per image (the error of the pixels kept when
+    the (j N) / K most uncertain, for S, or most wrong, for O, are removed), `.scalars` [B,6] AUSE_epe, AURG_epe, AUSE_d1, AURG_d1, N,
+    Nbad.  `[name]` and the attributes of the same names give views ([B,K] / [B]); `floats()` copies once to the host."""
+
+    def __init__(self, flat: torch.Tensor, B: int, K: int):
+        self._flat = flat                                  # one buffer behind both views: floats() is one copy
+        self.tensor = flat[:B * 4 * K].view(B, 4, K)
+        self.scalars = flat[B * 4 * K:].view(B, 6)
+
+    def __getitem__(self, name: str) -> torch.Tensor:
+        if name in CURVE_NAMES:
+            return self.tensor[:, CURVE_NAMES.index(name)]
+        return self.scalars[:, SCALAR_NAMES.index(name)]
+
+    def __getattr__(self, name: str) -> torch.Tensor:
+        if name in CURVE_NAMES or name in SCALAR_NAMES:
+            return self[name]
+        raise AttributeError(name)
+
+    def floats(self) -> Dict[str, list]:
+        """CURVE_NAMES -> B lists of K floats, SCALAR_NAMES -> B floats."""
+        B, _, K = self.tensor.shape
+        vals = self._flat.tolist()         # the only synchronisation
+        out: Dict[str, list] = {name: [vals[(b * 4 + c) * K:(b * 4 + c + 1) * K] for b in range(B)] for c, name in enumerate(CURVE_NAMES)}
+        s0 = B * 4 * K
+        out.update({name: [vals[s0 + b * 6 + c] for b in range(B)] for c, name in enumerate(SCALAR_NAMES)})
+        return out
+
+
+def _sparsify_inputs(disp: torch.Tensor, unc: torch.Tensor, gt: torch.Tensor):
+    if disp.dim() != 3 or unc.shape != disp.shape or gt.shape != disp.shape:
+        raise ValueError("sparsification: disp, unc and gt must all be [B, H, W]")
+    if disp.shape[1] * disp.shape[2] >= 2 ** 31:
+        raise ValueError("sparsification: H * W must stay below 2^31")
+
+
+def _kept_curve(key: torch.Tensor, e: torch.Tensor, bad: torch.Tensor, n: torch.Tensor):
+    """(sum of e, number of bad) over the n[j] pixels of smallest key, in float64; the group of equal keys a cut falls into gives
+    double(group sum) * double(kept of it) / double(its size), so the order inside a group never enters."""
+    ks, idx = torch.sort(key)
+    counts = torch.unique_consecutive(ks, return_counts=True)[1]
+    ends = counts.cumsum(0)
+    zero = ends.new_zeros(1)
+    out = []
+    gi = torch.searchsorted(ends, n)                       # the group that holds the n-th smallest key
+    m, c = (n - (ends[gi] - counts[gi])).double(), counts[gi].double()
+    for v in (e, bad):
+        incl = v[idx].cumsum(0)[ends - 1]                  # int64: exact
+        below = torch.cat((zero, incl[:-1]))
+        out.append(below[gi].double() + (incl[gi] - below[gi]).double() * m / c)
+    return out
+
+
+def _sparsify_image(d: torch.Tensor, u: torch.Tensor, g: torch.Tensor, maxdisp: float, K: int):
+    """(curves [4,K], scalars [6]) fp32 of one image: the definition of DESIGN.md 4.8.3 in int64 and float64."""
+    d, u, g = d.reshape(-1), u.reshape(-1), g.reshape(-1)
+    mask = (g > 0) & (g < torch.tensor(float(maxdisp), dtype=torch.float32, device=g.device)) & torch.isfinite(d) & torch.isfinite(u)
+    d, u, g = d[mask], u[mask], g[mask]
+    N = int(d.numel())
+    nan = float("nan")
+    if N == 0:
+        return torch.full((4, K), nan, device=d.device), torch.tensor([nan] * 4 + [0.0, 0.0], device=d.device)
+    e = torch.clamp(torch.round((d.double() - g.double()).abs() * 2.0 ** 20), max=_EQ_MAX).to(torch.int64)   # round: half to even
+    E = (g - d).abs()
+    bad = ((E > 3) & (E / g.abs() > torch.tensor(0.05, dtype=torch.float32, device=g.device))).to(torch.int64)   # D1's flag, in fp32
+    bits = u.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    bits = torch.where((bits & 0x7FFFFFFF) == 0, torch.zeros_like(bits), bits)                                  # -0 == +0
+    key = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)                                   # fp32's total order
+    j = torch.arange(K, dtype=torch.int64, device=d.device)
+    r = (j * N) // K
+    n = N - r
+    nd = n.double()
+    Nbad = int(bad.sum())
+    s_e, s_b = _kept_curve(key, e, bad, n)
+    o_e, _ = _kept_curve(e, e, bad, n)
+    curves = torch.stack((s_e * 2.0 ** -20 / nd, o_e * 2.0 ** -20 / nd, s_b / nd, torch.clamp(Nbad - r, min=0).double() / nd)).float()
+    rows = curves.double().tolist()
+
+    def mean(terms):                                       # float64, j ascending
+        a = 0.0
+        for t in terms:
+            a += t
+        return a / K
+    scal = [mean(s - o for s, o in zip(rows[0], rows[1])), mean(rows[0][0] - s for s in rows[0]),
+            mean(s - o for s, o in zip(rows[2], rows[3])), mean(rows[2][0] - s for s in rows[2]), float(N), float(Nbad)]
+    return curves, torch.tensor(scal, dtype=torch.float64, device=d.device).float()
+
+
+def _meter_of(meter, device, K: int) -> None:
+    if not isinstance(meter, CalibrationMeter) or meter.sums.device != device or meter.fractions != K:
+        raise ValueError("sparsification: meter must be a rag_amd.CalibrationMeter on the inputs' device with the same fractions")
+
+
+def sparsification_torch(disp: torch.Tensor, unc: torch.Tensor, gt: torch.Tensor, maxdisp: float = 192, fractions: int = 20,
+                         meter: Optional[CalibrationMeter] = None) -> Sparsification:
+    """Plain-torch twin of `sparsification` on the inputs' device: the same definition with torch.sort, unique_consecutive and int64 /
+    float64 sums (the CPU path, and the yardstick of the tests and tools/bench_sparsification.py)."""
+    K = _fractions(fractions)
+    _sparsify_inputs(disp, unc, gt)
+    if not maxdisp > 0:
+        raise ValueError("sparsification: maxdisp must be positive")
+    if meter is not None:
+        _meter_of(meter, disp.device, K)
+    with torch.no_grad():
+        d, u, g = (t.detach().float() for t in (disp, unc, gt))
+        rows = [_sparsify_image(d[b], u[b], g[b], maxdisp, K) for b in range(d.shape[0])]
+        curves, scalars = torch.stack([c for c, _ in rows]), torch.stack([s for _, s in rows])
+        if meter is not None:
+            counted = (scalars[:, 4] > 0).double()[:, None]
+            both = torch.cat((curves.reshape(len(rows), -1), scalars), dim=1).double()
+            meter.sums[:-1] += torch.where(counted > 0, both, torch.zeros_like(both)).sum(0)
+            meter.sums[-1] += counted.sum()
+        return Sparsification(torch.cat((curves.reshape(-1), scalars.reshape(-1))), len(rows), K)
+
+
+def sparsification(disp: torch.Tensor, unc: torch.Tensor, gt: torch.Tensor, maxdisp: float = 192, fractions: int = 20,
+                   meter: Optional[CalibrationMeter] = None) -> Sparsification:
+    """Does `unc` rank the errors of `disp`?  Per image of disp, unc, gt [B,H,W] (larger unc = less certain), over the pixels with
+    0 < gt < maxdisp and finite disp and unc: S_epe[j] / S_d1[j] are the EPE / D1 of the pixels kept after removing the (j N) / K most
+    uncertain (j < K = fractions), O_epe / O_d1 the same when the most wrong are removed instead; AUSE = mean_j(S - O) (0 for a perfect
+    ranking), AURG = mean_j(S[0] - S[j]) (the gain over random removal).  Equal uncertainties share their group's error in
+    proportion, so no tie order enters; errors are summed as integers of 2^-20 px, so the result is bitwise reproducible.  One fused
+    device pass without a sort: no synchronisation, no gather, capturable in a graph.  `meter`: the same launches
+    also add the images with a non-empty mask to that CalibrationMeter.  An image with an empty mask gives NaN curves and areas.  No
+    gradient; on CPU tensors the plain-torch twin runs."""
+    refuse_autograd("sparsification", disp, unc, gt)
+    if not disp.is_cuda:
+        return sparsification_torch(disp, unc, gt, maxdisp, fractions, meter)
+    K = _fractions(fractions)
+    ops._need_gpu(disp, unc, gt)
+    _sparsify_inputs(disp, unc, gt)
+    if meter is not None:
+        _meter_of(meter, disp.device, K)
+    with torch.no_grad():
+        d, u, g = disp.detach().contiguous(), unc.detach().contiguous(), gt.detach().contiguous()
+        B, H, W = d.shape
+        lib = load_library()
+        ws = torch.empty((max(1, lib.ragmi_sparsification_workspace_elems(B, H, W, K)), 2), device=d.device, dtype=torch.int64)
+        flat = torch.empty((B * (4 * K + 6),), device=d.device, dtype=torch.float32)
+        check(lib.ragmi_sparsification_fwd(d.data_ptr(), u.data_ptr(), g.data_ptr(), B, H, W, float(maxdisp), K, ws.data_ptr(),
+                                           flat.data_ptr(), flat.data_ptr() + 4 * B * 4 * K,
+                                           meter.sums.data_ptr() if meter is not None else None, ops._stream()), "sparsification")
+        return Sparsification(flat, B, K)
 
 
 # --------------------------------------------------------------------------- self-supervised loss (src_self, supervise=False)
