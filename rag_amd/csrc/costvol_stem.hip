@@ -24,6 +24,31 @@ namespace ragmi {
 
 constexpr int CS_MAXC = 16;                 // feature channels C and output channels Cout supported by the register tiles
 constexpr int CS_NCLS = 4, CS_NTC = 5;      // z-border classes; tc = -2..2 (tc = -3 contributes nothing)
+constexpr int CS_NVA = CS_NCLS * CS_NTC, CS_NVB = CS_NCLS * 2;      // variants: v = cls * CS_NTC + tcidx (A), CS_NVA + cls * 2 + xr (B)
+
+// admissible taps of a variant (file header): A by (dz, dx), B by (dz, e = dx - dz)
+__host__ __device__ constexpr bool cs_a_ok(int cls, int tc, int dx, int dz) {
+  return (dz >= 0 || !(cls & 1)) && (dz <= 0 || !(cls & 2)) && dz <= tc + dx;
+}
+__host__ __device__ constexpr bool cs_b_ok(int cls, int xr, int e, int dz) {
+  const int dx = e + dz;
+  return dx >= -1 && dx <= 1 && (dz >= 0 || !(cls & 1)) && (dz <= 0 || !(cls & 2)) && (dx < 1 || !xr);
+}
+// bit k: tap column k (dx = k - 1 / e = k - 2) of variant v has NO admissible dz — its pre-summed weight is a sum of nothing.  The
+// planes kernels leave such a column out instead of multiplying by that zero: the reference's cost volume holds a zero there, not
+// the feature, so a non-finite feature must not reach the plane through it (0 * Inf = NaN)
+__host__ __device__ constexpr unsigned cs_dead_taps(int v) {
+  unsigned m = 0;
+  const bool isb = v >= CS_NVA;
+  const int vb = v - CS_NVA;
+  for (int k = 0; k < (isb ? 5 : 3); ++k) {
+    bool live = false;
+    for (int dz = -1; dz <= 1; ++dz)
+      live = live || (isb ? cs_b_ok(vb / 2, vb % 2, k - 2, dz) : cs_a_ok(v / CS_NTC, v % CS_NTC - 2, k - 1, dz));
+    if (!live) m |= 1u << k;
+  }
+  return m;
+}
 
 // WA[cls][tcidx][c][dy][dx][co], WB[cls][xr][c][dy][e][co]  (co fastest: one broadcast LDS read feeds all outputs)
 __global__ __launch_bounds__(256) void costvol_stem_weights_kernel(const float* __restrict__ w, float* __restrict__ wa,
@@ -39,8 +64,7 @@ __global__ __launch_bounds__(256) void costvol_stem_weights_kernel(const float* 
     const int tc = t % CS_NTC - 2, cls = t / CS_NTC;
     float s = 0.f;
     for (int dz = -1; dz <= 1; ++dz) {
-      const bool ok = (dz >= 0 || !(cls & 1)) && (dz <= 0 || !(cls & 2)) && dz <= tc + dx;
-      if (ok) s += w[(((int64_t)co * 2 * C + c) * 3 + (dz + 1)) * 9 + dy * 3 + (dx + 1)];
+      if (cs_a_ok(cls, tc, dx, dz)) s += w[(((int64_t)co * 2 * C + c) * 3 + (dz + 1)) * 9 + dy * 3 + (dx + 1)];
     }
     wa[idx] = s;
   } else if (idx < na + nb) {
@@ -53,8 +77,7 @@ __global__ __launch_bounds__(256) void costvol_stem_weights_kernel(const float* 
     float s = 0.f;
     for (int dz = -1; dz <= 1; ++dz) {
       const int dx = e + dz;
-      const bool ok = dx >= -1 && dx <= 1 && (dz >= 0 || !(cls & 1)) && (dz <= 0 || !(cls & 2)) && (dx < 1 || !xr);
-      if (ok) s += w[(((int64_t)co * 2 * C + C + c) * 3 + (dz + 1)) * 9 + dy * 3 + (dx + 1)];
+      if (cs_b_ok(cls, xr, e, dz)) s += w[(((int64_t)co * 2 * C + C + c) * 3 + (dz + 1)) * 9 + dy * 3 + (dx + 1)];
     }
     wb[idx - na] = s;
   }
@@ -97,6 +120,7 @@ __global__ __launch_bounds__(CS_NT) void costvol_stem_planes_kernel(PlanesArgs a
   const int xb = blockIdx.x * CS_TX, yb = blockIdx.y * CS_TY;
   if (xb >= d.width) return;                                      // uniform: descriptors have different widths
   const int ntap = d.right ? 5 : 3, kh = d.right ? 2 : 1;
+  const unsigned dead = cs_dead_taps(d.variant);                  // uniform
   const T* src = static_cast<const T*>(d.right ? a.right : a.left) + (int64_t)b * a.C * a.H * a.W;
   const int nw = a.C * 3 * ntap * a.Cout;
   for (int e = threadIdx.x; e < nw; e += CS_NT) wl[e] = a.wts[d.w_off + e];
@@ -129,6 +153,7 @@ __global__ __launch_bounds__(CS_NT) void costvol_stem_planes_kernel(PlanesArgs a
           for (int k = 0; k < CS_PX + NT - 1; ++k) v[k] = tile[(cl * (CS_TY + 2) + yy + dy) * CS_RS + xx + k];
 #pragma unroll
           for (int k = 0; k < NT; ++k) {
+            if ((dead >> k) & 1u) continue;
             const float* wr = wl + ((c * 3 + dy) * NT + k) * a.Cout;
             if constexpr (COUT4 > 0) {
 #pragma unroll
@@ -186,7 +211,6 @@ __global__ __launch_bounds__(CS_NT) void costvol_stem_planes_kernel(PlanesArgs a
 // Weight fragments per variant (packed once per weight version by costvol_stem_pack_kernel, after the fp32 variants):
 //   wf[((v * NS + s) * 2 + hl) * 64 + lane] (uint4 = 8 halves of w * 2^k[co]),  wmul[v * 16 + co] = 2^-k[co]
 // with v = cls * CS_NTC + tcidx (A, NS = CS_NSA slices) or CS_NCLS * CS_NTC + cls * 2 + xr (B, CS_NSB slices: slots of CS_NSB each).
-constexpr int CS_NVA = CS_NCLS * CS_NTC, CS_NVB = CS_NCLS * 2;
 __host__ __device__ constexpr int cs_nslices(int C, int ntap) { return ((C / 4) * 3 * ntap + 7) / 8; }
 __host__ __device__ inline int64_t cs_frag_words(int C) {   // floats of all fragment slots + multipliers
   return ((int64_t)CS_NVA * cs_nslices(C, 3) + (int64_t)CS_NVB * cs_nslices(C, 5)) * 2 * 64 * 4 + (int64_t)(CS_NVA + CS_NVB) * 16;
@@ -230,6 +254,8 @@ __global__ __launch_bounds__(256) void costvol_stem_pack_kernel(const float* __r
 // owns rows 2w, 2w+1 (8 column tiles of 16), its weight fragments (NS slices, hi + lo) sit in registers.
 constexpr int CSM_TX = 64, CSM_TY = 8, CSM_HX = CSM_TX + 4, CSM_HY = CSM_TY + 2, CSM_THREADS = 256;
 constexpr int CSM_RS = CSM_HX + 1;                         // record stride of a halo row (8-byte records)
+constexpr int CSM_NZ = CSM_RS + 3 * 16 + 1;                // zero records behind the halo: what a pair that contributes nothing reads, at each of
+                                                           // a wave's 8 tile offsets (t >> 2) * CSM_RS + (t & 3) * 16
 template <class TF, int NCG, int NTAP>
 __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& a, const PlaneDesc& d, const uint4* __restrict__ frag_a,
                                                               const uint4* __restrict__ frag_b, const float* __restrict__ wmul_all,
@@ -241,6 +267,7 @@ __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, kb = lane >> 4;
   const TF* const src = static_cast<const TF*>(d.right ? a.right : a.left) + (int64_t)b * a.C * a.H * a.W;      // TF: the features' storage type
   if (tid == 0) lmax = 0u;
+  if (tid < CSM_NZ) lhi[NCG * CSM_HY * CSM_RS + tid] = llo[NCG * CSM_HY * CSM_RS + tid] = make_uint2(0u, 0u);
   // halo records of this thread: 4 channels of one (row, column)
   float pf[NPF][4];
   unsigned valid = 0;
@@ -261,15 +288,6 @@ __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& 
   uint4 ah[NS], al[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) { ah[s] = wf[(s * 2 + 0) * 64 + lane]; al[s] = wf[(s * 2 + 1) * 64 + lane]; }
-  // operand record offsets of this lane quarter: slice s, pair j -> (tap, cg) -> (cg * HY + dy) * RS + k   (padding pairs: pair 0's)
-  int poff[NS][2];
-#pragma unroll
-  for (int s = 0; s < NS; ++s)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int P = 8 * s + 2 * kb + j, tap = P / NCG, cg = P % NCG;
-      poff[s][j] = tap < 3 * NTAP ? (cg * CSM_HY + tap / NTAP) * CSM_RS + tap % NTAP : 0;
-    }
   float m = 0.f;
 #pragma unroll
   for (int p = 0; p < NPF; ++p) {
@@ -294,6 +312,20 @@ __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& 
     llo[dst] = make_uint2(l01, l23);
   }
   __syncthreads();
+  // operand records of this lane: its first tile's (row 2 * wave, column n) + slice s, pair j -> (tap, cg) -> (cg * HY + dy) * RS + k.
+  // Padding pairs and tap columns without an admissible dz (cs_dead_taps) have zero weights: they read the zero records, so that a
+  // non-finite feature does not reach the plane through them.  (Computed here, behind the commit: next to the 32 halo registers they
+  // cost the kernel a wave of occupancy — 137 VGPRs against 118.)
+  const unsigned dead = cs_dead_taps(v);
+  int poff[NS][2];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int P = 8 * s + 2 * kb + j, tap = P / NCG, cg = P % NCG;
+      poff[s][j] = (tap < 3 * NTAP && !((dead >> (tap % NTAP)) & 1u)) ? 2 * wave * CSM_RS + n + (cg * CSM_HY + tap / NTAP) * CSM_RS + tap % NTAP
+                                                                      : NCG * CSM_HY * CSM_RS;
+    }
   const float inv = 1.f / mul;
   float osc[4];
 #pragma unroll
@@ -302,7 +334,7 @@ __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& 
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
     const int row = 2 * wave + (t >> 2), col = (t & 3) * 16 + n;      // tile t of this wave: row, 16 columns
-    const int base = row * CSM_RS + col;
+    const int base = (t >> 2) * CSM_RS + (t & 3) * 16;               // this tile's offset from the lane's first
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -313,7 +345,7 @@ __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& 
       acc = x3_mma<false>(al[s], bh, acc);
     }
     const int y = yb + row, xi = xb + col;
-    if (y < a.H && xi < d.width && 4 * kb < a.Cout) {      // [y][xi][Cout] (Cout a multiple of 4 here): this lane's four channels are 16 bytes
+    if (y < a.H && xi < d.width && 4 * kb < a.Cout) {      // [y][xi][Cout] (Cout a multiple of 4: stem_run): this lane's four channels are 16 bytes
       *reinterpret_cast<float4*>(out + ((int64_t)y * d.width + xi) * a.Cout + 4 * kb) =
           make_float4(acc[0] * osc[0], acc[1] * osc[1], acc[2] * osc[2], acc[3] * osc[3]);
     }
@@ -325,7 +357,7 @@ __device__ __forceinline__ void costvol_stem_planes_mfma_body(const PlanesArgs& 
 template <int NCG, class TF = float>
 __global__ __launch_bounds__(CSM_THREADS, 2) void costvol_stem_planes_mfma_kernel(PlanesArgs a, const uint4* __restrict__ frag_a,
                                                                                  const uint4* __restrict__ frag_b, const float* __restrict__ wmul_all) {
-  __shared__ __attribute__((aligned(16))) uint2 lhi[NCG * CSM_HY * CSM_RS], llo[NCG * CSM_HY * CSM_RS];
+  __shared__ __attribute__((aligned(16))) uint2 lhi[NCG * CSM_HY * CSM_RS + CSM_NZ], llo[NCG * CSM_HY * CSM_RS + CSM_NZ];
   __shared__ unsigned lmax;
   const PlaneDesc d = a.d[blockIdx.z % a.ndesc];
   if ((int)blockIdx.x * CSM_TX >= d.width) return;               // uniform: descriptors have different widths
@@ -632,10 +664,12 @@ static int stem_run(const void* left, const void* right, const void* variants, c
   RAGMI_REQUIRE(conv_dtype_ok(dtype), RAGMI_EUNSUPPORTED, "costvol_stem: dtype %d not built", dtype);
   RAGMI_REQUIRE(ntail >= 0 && ntail <= 2 && (ntail == 0 || tails), RAGMI_EINVAL, "costvol_stem: at most two tails");
   // RAGMI_F32X3: fp32 storage, the variant planes as split-operand products on the matrix cores where the shape allows
-  // (whole 4-channel groups, <= 12 feature channels); everything else of this entry point is fp32 either way
+  // (whole 4-channel groups, <= 12 feature channels; whole 4-channel groups of OUTPUTS too: that kernel stores a lane quarter's four
+  // channels as 16 bytes, which in a [y][xi][Cout] row of a ragged Cout would run into the next pixel); everything else of this entry
+  // point is fp32 either way
   // (round 5: bf16 features too — the planes are fp32 in the workspace either way, and under bf16 storage everything downstream of them
   // is rounded to 8 bits)
-  const bool mfma_planes = (dtype == RAGMI_F32X3 || dtype == RAGMI_BF16) && C % 4 == 0 && C <= 12;
+  const bool mfma_planes = (dtype == RAGMI_F32X3 || dtype == RAGMI_BF16) && C % 4 == 0 && C <= 12 && Cout % 4 == 0;
   const bool bf_features = dtype == RAGMI_BF16;
   if (dtype == RAGMI_F32X3) dtype = RAGMI_F32;
   StemLayout l;

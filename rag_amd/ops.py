@@ -318,9 +318,11 @@ def costvol_stem_prepare(weight: torch.Tensor) -> torch.Tensor:
 
 def costvol_stem(left_fea: torch.Tensor, right_fea: torch.Tensor, maxdisp: int, variants: torch.Tensor, cout: int,
                  scale: Optional[torch.Tensor], shift: Optional[torch.Tensor], relu: bool, out: Optional[torch.Tensor] = None,
-                 tails: Optional[Sequence[Tail]] = None, out_g4: bool = False) -> torch.Tensor:
+                 tails: Optional[Sequence[Tail]] = None, out_g4: bool = False, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(bn(conv3x3x3(cost_volume(left_fea, right_fea)))) without building the cost volume: ragmi_costvol_stem_fwd.
-    out_g4: `out` is written channel-group-interleaved (RAGMI_CONV_Y_G4)."""
+    out_g4: `out` is written channel-group-interleaved (RAGMI_CONV_Y_G4).
+    workspace: the caller's buffer for the variant planes instead of a fresh one (fp32, contiguous, on the features' device,
+    16-byte aligned, at least ragmi_costvol_stem_workspace_elems elements)."""
     _need_gpu(variants, scale, shift)
     dt = _act(left_fea, right_fea, out, *[t.out for t in (tails or [])])
     if left_fea.shape != right_fea.shape or left_fea.dim() != 4:
@@ -333,7 +335,15 @@ def costvol_stem(left_fea: torch.Tensor, right_fea: torch.Tensor, maxdisp: int, 
     if tuple(out.shape[2:]) != (d, h, w) or out.shape[1] < cout or out.shape[0] != B:
         raise ValueError("costvol_stem: out must be [B, >=Cout, maxdisp/3, h, w]")
     lib = load_library()
-    ws = torch.empty((lib.ragmi_costvol_stem_workspace_elems(B, C, cout, d, h, w),), device=left_fea.device, dtype=torch.float32)
+    ws_elems = lib.ragmi_costvol_stem_workspace_elems(B, C, cout, d, h, w)
+    if workspace is None:
+        ws = torch.empty((ws_elems,), device=left_fea.device, dtype=torch.float32)
+    else:
+        ws = workspace
+        if (ws.dtype != torch.float32 or ws.device != left_fea.device or not ws.is_contiguous() or ws.data_ptr() % 16
+                or ws.numel() < ws_elems):
+            raise ValueError(f"costvol_stem: workspace must be a contiguous, 16-byte aligned fp32 tensor of at least {ws_elems} elements "
+                             "on the features' device")
     ntail, tarr = _tail_array(tails)
     p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     if out_g4 and (not out.is_contiguous() or out.shape[1] != cout):
