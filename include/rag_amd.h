@@ -574,7 +574,8 @@ int ragmi_conv3d_k3_pack_for(const void* weight, void* packed, int Cout, int Cin
 /* Train-mode BatchNorm3d statistics (operations_3d.py:44) of the raw conv output x[B,C,DHW]: batch mean / biased variance ->
  * mean[c], invstd[c], scale[c] = gamma*invstd, shift[c] = beta - mean*scale, and (running_mean != NULL) the momentum update of
  * running_mean / running_var (unbiased) / num_batches_tracked (int64, may be NULL) with nn.BatchNorm semantics.  Two-level
- * deterministic reduction; `workspace` holds ragmi_bn_workspace_elems(B, C, DHW) floats (no initialisation needed). */
+ * deterministic reduction of x - K and (x - K)^2 about the channel's pivot K = x[0,c,0] (mean = K + s/n, var = q/n - (s/n)^2: no
+ * (mean/std)^2 cancellation); `workspace` holds ragmi_bn_workspace_elems(B, C, DHW) floats (no initialisation needed). */
 int64_t ragmi_bn_workspace_elems(int B, int C, int64_t DHW);
 int ragmi_bn_train_stats_fwd(const void* x, int64_t x_bstride, int B, int C, int64_t DHW, const void* gamma, const void* beta,
                              void* running_mean, void* running_var, void* num_batches_tracked, float momentum, float eps,
@@ -582,14 +583,15 @@ int ragmi_bn_train_stats_fwd(const void* x, int64_t x_bstride, int B, int C, int
 
 /* the two launches of a train-mode BatchNorm + ReLU forward: statistics, then finalize (as ragmi_bn_train_stats_fwd) fused with the
  * affine + ReLU pass y[b, y_ch0+c] = act(x[b,c]*scale[c] + shift[c]) (+ res[b, res_ch0+c] when res != NULL: a cell's running sum of
- * branches, rag_model.py:163-172, without a separate add launch) */
+ * branches, rag_model.py:163-172, without a separate add launch).  y must not overlap x: every workgroup of the second launch
+ * reads the channel's pivot x[0,c,0] while others store y (res may be y's buffer only where the same element is read and written) */
 int ragmi_bn_train_act_fwd(const void* x, int64_t x_bstride, int B, int C, int64_t DHW, const void* gamma, const void* beta,
                            void* running_mean, void* running_var, void* num_batches_tracked, float momentum, float eps, int relu,
                            void* workspace, void* mean, void* invstd, void* scale, void* shift, void* y, int64_t y_bstride, int y_ch0,
                            const void* res, int64_t res_bstride, int res_ch0, void* stream);
 
-/* the two launches of its adjoint: the reduction of ragmi_bn_act_bwd_coeffs, then coefficients + dx = g*c1 + x*c2 + c3 in one pass
- * (dgamma / dbeta may be NULL; accumulate != 0: +=) */
+/* the two launches of its adjoint: the reduction of ragmi_bn_act_bwd_coeffs, then coefficients + dx = g*c1 + (x - mean)*c2 + c3 in
+ * one pass (dgamma / dbeta may be NULL; accumulate != 0: +=) */
 int ragmi_bn_act_bwd(const void* dy, int64_t dy_bstride, int dy_ch0, const void* x, int64_t x_bstride, const void* scale,
                      const void* shift, int relu, const void* mean, const void* invstd, int training, int B, int C, int64_t DHW,
                      void* workspace, void* dx, int64_t dx_bstride, void* dgamma, void* dbeta, int accumulate, void* stream);
@@ -600,17 +602,18 @@ int ragmi_bn_act_fwd(const void* x, int64_t x_bstride, const void* scale, const 
                      void* y, int64_t y_bstride, int y_ch0, int B, int C, int64_t DHW, void* stream);
 
 /* ReLU + BatchNorm adjoint, reduction half: with g = dy * [x*scale+shift > 0] (x = the raw conv output) it reduces sum g and
- * sum g*x per channel and writes dgamma[c], dbeta[c] and the coefficients of dx = g*c1 + x*c2 + c3 (training != 0: batch
- * statistics were used; 0: running statistics, c2 = c3 = 0).  Same workspace as ragmi_bn_train_stats_fwd. */
+ * sum g*(x - mean) per channel and writes dgamma[c], dbeta[c] and the coefficients of dx = g*c1 + (x - c0)*c2 + c3 with c0 = mean
+ * (training != 0: batch statistics were used; 0: running statistics, c2 = c3 = 0).  The form is centred on the mean so that nothing
+ * of the size of mean*c2 has to cancel in fp32.  Same workspace as ragmi_bn_train_stats_fwd. */
 int ragmi_bn_act_bwd_coeffs(const void* dy, int64_t dy_bstride, int dy_ch0, const void* x, int64_t x_bstride,
                             const void* scale, const void* shift, int relu, const void* mean, const void* invstd, int training,
-                            int B, int C, int64_t DHW, void* workspace, void* c1, void* c2, void* c3, void* dgamma, void* dbeta,
-                            int accumulate, void* stream);   /* dgamma / dbeta may be NULL; accumulate != 0: += */
+                            int B, int C, int64_t DHW, void* workspace, void* c0, void* c1, void* c2, void* c3, void* dgamma,
+                            void* dbeta, int accumulate, void* stream);   /* dgamma / dbeta may be NULL; accumulate != 0: += */
 
-/* dx[b,c] = g * c1[c] + x * c2[c] + c3[c]   (train-mode BN backward is linear in g and x per channel; eval BN: c2 = c3 = 0) */
+/* dx[b,c] = g * c1[c] + (x - c0[c]) * c2[c] + c3[c]   (train-mode BN backward is linear in g and x per channel; eval BN: c2 = c3 = 0) */
 int ragmi_bn_act_bwd_apply(const void* dy, int64_t dy_bstride, int dy_ch0, const void* x, int64_t x_bstride,
-                           const void* scale, const void* shift, int relu, const void* c1, const void* c2, const void* c3,
-                           void* dx, int64_t dx_bstride, int B, int C, int64_t DHW, void* stream);
+                           const void* scale, const void* shift, int relu, const void* c0, const void* c1, const void* c2,
+                           const void* c3, void* dx, int64_t dx_bstride, int B, int C, int64_t DHW, void* stream);
 
 /* dw[co][ci][tap] = sum_{b,v} g[b, g_ch0+co, v] * x[b, ci, v + tap]   — weight gradient of the 3x3x3 conv (MFMA; persistent
  * workgroups write partial sums to `workspace`, ragmi_conv3d_k3_wgrad_workspace_elems(...) floats, and a second kernel adds them:

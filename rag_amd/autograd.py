@@ -177,8 +177,8 @@ def _bn_backward(dy, raw, scale, shift, mean, invstd, mod, n, training, need_g, 
         return dx, dgamma, dbeta
     else:
         c1 = scale
-        c2 = c3 = torch.zeros_like(scale)
-    return ops.bn_act_bwd_apply(dy, 0, raw, scale, shift, mod.relu, c1, c2, c3, out=out), dgamma, dbeta
+        c0 = c2 = c3 = torch.zeros_like(scale)
+    return ops.bn_act_bwd_apply(dy, 0, raw, scale, shift, mod.relu, c0, c1, c2, c3, out=out), dgamma, dbeta
 
 
 class ConvBRGroupFn(torch.autograd.Function):

@@ -37,21 +37,37 @@ __device__ __forceinline__ void block_pair_sum(const float* __restrict__ part, i
   s = ds[0]; q = dq[0];
 }
 
-// partial (sum, sum of squares) of x[B, C, DHW] (batch stride in elements; channel planes dense)
+// partial (sum, sum of squares) of x[B, C, DHW] - K (batch stride in elements; channel planes dense).  The sums are taken about
+// the channel's pivot K = x[0, c, 0] (its first element in batch 0: known without a pass of its own), and bn_moments() forms
+// mean = K + s/n, var = q/n - (s/n)^2: the cancellation of the raw form q/n - mean^2 grows like (mean/std)^2 (a channel of mean
+// 1000, std 1 lost the variance's second digit), about the pivot it grows like ((mean - K)/std)^2, and K is a sample of the channel.
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int64_t x_bstride, int64_t dhw,
                                                        float* __restrict__ part, int nparts) {
   const int c = blockIdx.y, b = blockIdx.z;
+  const float K = x[(int64_t)c * dhw];
   const float* p = x + b * x_bstride + (int64_t)c * dhw;
   const bool vec = (dhw & 3) == 0 && ((reinterpret_cast<uintptr_t>(p) & 15) == 0);
   float s = 0.f, q = 0.f;
-  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < dhw; i += (int64_t)gridDim.x * 1024) {
-    if (vec) {
-      const float4 v = *reinterpret_cast<const float4*>(p + i);
+  const int64_t step = (int64_t)gridDim.x * 1024;
+  int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (vec) {
+    auto quad = [&](float4 v) {
+      v.x -= K; v.y -= K; v.z -= K; v.w -= K;
       s += (v.x + v.y) + (v.z + v.w);
       q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-    } else {
-      for (int k = 0; k < 4 && i + k < dhw; ++k) { const float v = p[i + k]; s += v; q += v * v; }
+    };
+    // two quads per trip, both loads issued before either is used: a trip waits for its loads before the next is issued, so the
+    // loop is bound by the load's latency and, one quad at a time, the pivot's subtractions showed in the training step
+    // (+0.02 ms).  Summed in the order of the one-quad loop.
+    for (; i + step < dhw; i += 2 * step) {
+      const float4 v0 = *reinterpret_cast<const float4*>(p + i), v1 = *reinterpret_cast<const float4*>(p + i + step);
+      quad(v0);
+      quad(v1);
     }
+    if (i < dhw) quad(*reinterpret_cast<const float4*>(p + i));
+  } else {
+    for (; i < dhw; i += step)
+      for (int k = 0; k < 4 && i + k < dhw; ++k) { const float v = p[i + k] - K; s += v; q += v * v; }
   }
   block_pair_store(s, q, part, (int64_t)c * nparts + (int64_t)b * gridDim.x + blockIdx.x);
 }
@@ -73,14 +89,22 @@ struct BnFinalizeArgs {
   double n;
   float eps, momentum;
 };
-__global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinalizeArgs a) {
+// batch mean and biased variance of a channel from the sums (s, q) of x - K and (x - K)^2.  The callers load K = x[c * dhw] BEFORE
+// block_pair_sum: behind its barriers the load's latency would sit on the critical path of every workgroup.
+__device__ __forceinline__ void bn_moments(const BnFinalizeArgs& a, float K, double s, double q, double& mean, double& var) {
+  const double d = s / a.n;
+  mean = (double)K + d;
+  var = q / a.n - d * d;
+  var = var > 0.0 ? var : 0.0;
+}
+__global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinalizeArgs a, const float* __restrict__ x, int64_t dhw) {
   const int c = blockIdx.x;
+  const float K = x[(int64_t)c * dhw];
   double s, q;
   block_pair_sum(a.part, a.nparts, c, s, q);
   if (threadIdx.x != 0) return;
-  const double mean = s / a.n;
-  double var = q / a.n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
+  double mean, var;
+  bn_moments(a, K, s, q, mean, var);
   const float invstd = (float)(1.0 / sqrt(var + (double)a.eps));
   const float sc = a.gamma[c] * invstd;
   a.mean[c] = (float)mean;
@@ -122,39 +146,51 @@ __global__ __launch_bounds__(256) void bn_act_kernel(const float* __restrict__ x
   }
 }
 
-// g = dy * (x*scale+shift > 0 if relu);  partial (sum g, sum g*x) per workgroup
+// g = dy * (x*scale+shift > 0 if relu);  partial (sum g, sum g*(x - mean)) per workgroup.  Centred: sum g*x - mean * sum g cancels
+// like |mean|/std, and what is left of it is dgamma and the x coefficient of dx.
 __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const float* __restrict__ dy, int64_t dy_bstride, int dy_ch0,
                                                                 const float* __restrict__ x, int64_t x_bstride,
                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                int relu, int64_t dhw, float* __restrict__ part, int nparts) {
+                                                                const float* __restrict__ mean, int relu, int64_t dhw,
+                                                                float* __restrict__ part, int nparts) {
   const int c = blockIdx.y, b = blockIdx.z;
   const float* pd = dy + b * dy_bstride + (int64_t)(dy_ch0 + c) * dhw;
   const float* px = x + b * x_bstride + (int64_t)c * dhw;
-  const float sc = scale[c], sh = shift[c];
+  const float sc = scale[c], sh = shift[c], mu = mean[c];
   const bool vec = (dhw & 3) == 0 && (((reinterpret_cast<uintptr_t>(pd) | reinterpret_cast<uintptr_t>(px)) & 15) == 0);
   float s = 0.f, q = 0.f;
   auto one = [&](float g, float xv) {
     if (relu && fmaf(xv, sc, sh) <= 0.f) g = 0.f;
     s += g;
-    q = fmaf(g, xv, q);
+    q = fmaf(g, xv - mu, q);
   };
-  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < dhw; i += (int64_t)gridDim.x * 1024) {
-    if (vec) {
-      const float4 g4 = *reinterpret_cast<const float4*>(pd + i), x4 = *reinterpret_cast<const float4*>(px + i);
-      one(g4.x, x4.x); one(g4.y, x4.y); one(g4.z, x4.z); one(g4.w, x4.w);
-    } else {
-      for (int k = 0; k < 4 && i + k < dhw; ++k) one(pd[i + k], px[i + k]);
+  const int64_t step = (int64_t)gridDim.x * 1024;
+  int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (vec) {
+    auto quad = [&](const float4& g4, const float4& x4) { one(g4.x, x4.x); one(g4.y, x4.y); one(g4.z, x4.z); one(g4.w, x4.w); };
+    // two quads per trip, their four loads issued before any is used; summed in the order of the one-quad loop
+    for (; i + step < dhw; i += 2 * step) {
+      const float4 g0 = *reinterpret_cast<const float4*>(pd + i), x0 = *reinterpret_cast<const float4*>(px + i);
+      const float4 g1 = *reinterpret_cast<const float4*>(pd + i + step), x1 = *reinterpret_cast<const float4*>(px + i + step);
+      quad(g0, x0);
+      quad(g1, x1);
     }
+    if (i < dhw) quad(*reinterpret_cast<const float4*>(pd + i), *reinterpret_cast<const float4*>(px + i));
+  } else {
+    for (; i < dhw; i += step)
+      for (int k = 0; k < 4 && i + k < dhw; ++k) one(pd[i + k], px[i + k]);
   }
   block_pair_store(s, q, part, (int64_t)c * nparts + (int64_t)b * gridDim.x + blockIdx.x);
 }
 
-// per-channel coefficients of the ReLU+BN adjoint dx = g*c1 + x*c2 + c3, plus dgamma / dbeta
+// per-channel coefficients of the ReLU+BN adjoint dx = g*c1 + (x - c0)*c2 + c3 (c0 = mean: the centred form, no term of the size
+// of mean * c2 to cancel against x * c2), plus dgamma / dbeta
 struct BnCoeffArgs {
   const float* part;
   const float* mean;
   const float* invstd;
   const float* scale;
+  float* c0;
   float* c1;
   float* c2;
   float* c3;
@@ -165,19 +201,20 @@ struct BnCoeffArgs {
 };
 __global__ __launch_bounds__(256) void bn_bwd_coeffs_kernel(BnCoeffArgs a) {
   const int c = blockIdx.x;
-  double sg, sgx;
-  block_pair_sum(a.part, a.nparts, c, sg, sgx);
+  double sg, sgxc;
+  block_pair_sum(a.part, a.nparts, c, sg, sgxc);
   if (threadIdx.x != 0) return;
-  const double mean = a.mean[c], invstd = a.invstd[c], sc = a.scale[c];
-  const double sgxh = invstd * (sgx - mean * sg);          // sum of g * xhat
+  const double invstd = a.invstd[c], sc = a.scale[c];
+  const double sgxh = invstd * sgxc;                       // sum of g * xhat
   if (a.dgamma) a.dgamma[c] = (a.accumulate ? a.dgamma[c] : 0.f) + (float)sgxh;
   if (a.dbeta) a.dbeta[c] = (a.accumulate ? a.dbeta[c] : 0.f) + (float)sg;
+  a.c0[c] = a.mean[c];
   a.c1[c] = (float)sc;
   if (a.training) {
     // dx = a (g - mean(g) - xhat mean(g xhat)), a = gamma * invstd: linear in g and x per channel
     const double mg = sg / a.n, mgxh = sgxh / a.n;
     a.c2[c] = (float)(-sc * invstd * mgxh);
-    a.c3[c] = (float)(sc * (invstd * mean * mgxh - mg));
+    a.c3[c] = (float)(-sc * mg);
   } else {
     a.c2[c] = 0.f;
     a.c3[c] = 0.f;
@@ -200,11 +237,11 @@ struct BnFinActArgs {
 };
 __global__ __launch_bounds__(256) void bn_finalize_act_kernel(BnFinActArgs a) {
   const int c = blockIdx.y, b = blockIdx.z;
+  const float K = a.x[(int64_t)c * a.dhw];      // read by every workgroup of the channel: y must not overlap x
   double s, q;
   block_pair_sum(a.f.part, a.f.nparts, c, s, q);
-  const double mean = s / a.f.n;
-  double var = q / a.f.n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
+  double mean, var;
+  bn_moments(a.f, K, s, q, mean, var);
   const float invstd = (float)(1.0 / sqrt(var + (double)a.f.eps));
   const float sc = a.f.gamma[c] * invstd, sh = a.f.beta[c] - (float)mean * sc;
   if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
@@ -259,10 +296,10 @@ struct BnCoeffApplyArgs {
 };
 __global__ __launch_bounds__(256) void bn_coeffs_apply_kernel(BnCoeffApplyArgs a) {
   const int c = blockIdx.y, b = blockIdx.z;
-  double sg, sgx;
-  block_pair_sum(a.part, a.nparts, c, sg, sgx);
-  const double mean = a.mean[c], invstd = a.invstd[c], scd = a.scale[c];
-  const double sgxh = invstd * (sgx - mean * sg);          // sum of g * xhat
+  double sg, sgxc;
+  block_pair_sum(a.part, a.nparts, c, sg, sgxc);
+  const double invstd = a.invstd[c], scd = a.scale[c];
+  const double sgxh = invstd * sgxc;                       // sum of g * xhat
   if (blockIdx.x == 0 && b == 0 && threadIdx.x == 0) {
     if (a.dgamma) a.dgamma[c] = (a.accumulate ? a.dgamma[c] : 0.f) + (float)sgxh;
     if (a.dbeta) a.dbeta[c] = (a.accumulate ? a.dbeta[c] : 0.f) + (float)sg;
@@ -271,17 +308,17 @@ __global__ __launch_bounds__(256) void bn_coeffs_apply_kernel(BnCoeffApplyArgs a
   if (a.training) {
     const double mg = sg / a.n, mgxh = sgxh / a.n;
     k2 = (float)(-scd * invstd * mgxh);
-    k3 = (float)(scd * (invstd * mean * mgxh - mg));
+    k3 = (float)(-scd * mg);
   }
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i0 >= a.dhw) return;
   const float* px = a.x + b * a.x_bstride + (int64_t)c * a.dhw;
   const float* pg = a.dy + b * a.dy_bstride + (int64_t)(a.dy_ch0 + c) * a.dhw;
   float* po = a.dx + b * a.dx_bstride + (int64_t)c * a.dhw;
-  const float sc = a.scale[c], sh = a.shift[c];
+  const float sc = a.scale[c], sh = a.shift[c], k0 = a.mean[c];
   auto one = [&](float g, float xv) {
     if (a.relu && fmaf(xv, sc, sh) <= 0.f) g = 0.f;
-    return fmaf(g, k1, fmaf(xv, k2, k3));
+    return fmaf(g, k1, fmaf(xv - k0, k2, k3));
   };
   const uintptr_t al = reinterpret_cast<uintptr_t>(px) | reinterpret_cast<uintptr_t>(pg) | reinterpret_cast<uintptr_t>(po);
   if ((a.dhw & 3) == 0 && (al & 15) == 0) {
@@ -292,12 +329,12 @@ __global__ __launch_bounds__(256) void bn_coeffs_apply_kernel(BnCoeffApplyArgs a
   }
 }
 
-// dx[b, c] = g * c1[c] + x * c2[c] + c3[c]   (train-mode BN backward is linear in g and x per channel; eval: c2 = c3 = 0)
+// dx[b, c] = g * c1[c] + (x - c0[c]) * c2[c] + c3[c]   (train-mode BN backward is linear in g and x per channel; eval: c2 = c3 = 0)
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const float* __restrict__ dy, int64_t dy_bstride, int dy_ch0,
                                                                const float* __restrict__ x, int64_t x_bstride,
                                                                const float* __restrict__ scale, const float* __restrict__ shift,
-                                                               int relu, const float* __restrict__ c1, const float* __restrict__ c2,
-                                                               const float* __restrict__ c3, float* __restrict__ dx,
+                                                               int relu, const float* __restrict__ c0, const float* __restrict__ c1,
+                                                               const float* __restrict__ c2, const float* __restrict__ c3, float* __restrict__ dx,
                                                                int64_t dx_bstride, int64_t dhw) {
   const int c = blockIdx.y, b = blockIdx.z;
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -305,10 +342,10 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const float* __re
   const float* px = x + b * x_bstride + (int64_t)c * dhw;
   const float* pg = dy + b * dy_bstride + (int64_t)(dy_ch0 + c) * dhw;
   float* po = dx + b * dx_bstride + (int64_t)c * dhw;
-  const float sc = scale[c], sh = shift[c], k1 = c1[c], k2 = c2[c], k3 = c3[c];
+  const float sc = scale[c], sh = shift[c], k0 = c0[c], k1 = c1[c], k2 = c2[c], k3 = c3[c];
   auto one = [&](float g, float xv) {
     if (relu && fmaf(xv, sc, sh) <= 0.f) g = 0.f;
-    return fmaf(g, k1, fmaf(xv, k2, k3));
+    return fmaf(g, k1, fmaf(xv - k0, k2, k3));
   };
   const uintptr_t al = reinterpret_cast<uintptr_t>(px) | reinterpret_cast<uintptr_t>(pg) | reinterpret_cast<uintptr_t>(po);
   if ((dhw & 3) == 0 && (al & 15) == 0) {
@@ -881,7 +918,7 @@ extern "C" int ragmi_bn_train_stats_fwd(const void* x, int64_t x_bstride, int B,
   BnFinalizeArgs a{(const float*)workspace, (const float*)gamma, (const float*)beta, (float*)running_mean, (float*)running_var,
                    (long long*)num_batches_tracked, (float*)mean, (float*)invstd, (float*)scale, (float*)shift, nparts,
                    (double)B * (double)DHW, eps, momentum};
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, st, a, (const float*)x, DHW);
   return check_launch("bn_train_stats");
 }
 
@@ -919,7 +956,7 @@ extern "C" int ragmi_bn_act_bwd(const void* dy, int64_t dy_bstride, int dy_ch0, 
   const int nparts = (int)(gx * B);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3(gx, C, B), dim3(256), 0, st, (const float*)dy, dy_bstride, dy_ch0, (const float*)x,
-                     x_bstride, (const float*)scale, (const float*)shift, relu, DHW, (float*)workspace, nparts);
+                     x_bstride, (const float*)scale, (const float*)shift, (const float*)mean, relu, DHW, (float*)workspace, nparts);
   BnCoeffApplyArgs a{};
   a.part = (const float*)workspace; a.mean = (const float*)mean; a.invstd = (const float*)invstd; a.scale = (const float*)scale;
   a.shift = (const float*)shift; a.dgamma = (float*)dgamma; a.dbeta = (float*)dbeta; a.dy = (const float*)dy; a.x = (const float*)x;
@@ -943,32 +980,33 @@ extern "C" int ragmi_bn_act_fwd(const void* x, int64_t x_bstride, const void* sc
 
 extern "C" int ragmi_bn_act_bwd_coeffs(const void* dy, int64_t dy_bstride, int dy_ch0, const void* x, int64_t x_bstride,
                                       const void* scale, const void* shift, int relu, const void* mean, const void* invstd, int training,
-                                      int B, int C, int64_t DHW, void* workspace, void* c1, void* c2, void* c3, void* dgamma, void* dbeta,
-                                      int accumulate, void* stream) {
+                                      int B, int C, int64_t DHW, void* workspace, void* c0, void* c1, void* c2, void* c3, void* dgamma,
+                                      void* dbeta, int accumulate, void* stream) {
   using namespace ragmi;
-  RAGMI_REQUIRE(dy && x && scale && shift && mean && invstd && workspace && c1 && c2 && c3, RAGMI_EINVAL,
+  RAGMI_REQUIRE(dy && x && scale && shift && mean && invstd && workspace && c0 && c1 && c2 && c3, RAGMI_EINVAL,
                 "bn_act_bwd_coeffs: null pointer");
   RAGMI_REQUIRE(B > 0 && C > 0 && DHW > 0 && B <= 65535 && C <= 65535, RAGMI_EINVAL, "bn_act_bwd_coeffs: bad size");
   const unsigned gx = reduce_blocks(B, C, DHW);
   const int nparts = (int)(gx * B);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3(gx, C, B), dim3(256), 0, st, (const float*)dy, dy_bstride, dy_ch0, (const float*)x,
-                     x_bstride, (const float*)scale, (const float*)shift, relu, DHW, (float*)workspace, nparts);
-  BnCoeffArgs a{(const float*)workspace, (const float*)mean, (const float*)invstd, (const float*)scale, (float*)c1, (float*)c2, (float*)c3,
+                     x_bstride, (const float*)scale, (const float*)shift, (const float*)mean, relu, DHW, (float*)workspace, nparts);
+  BnCoeffArgs a{(const float*)workspace, (const float*)mean, (const float*)invstd, (const float*)scale, (float*)c0, (float*)c1, (float*)c2,
+                (float*)c3,
                 (float*)dgamma, (float*)dbeta, nparts, training ? 1 : 0, accumulate ? 1 : 0, (double)B * (double)DHW};
   hipLaunchKernelGGL(bn_bwd_coeffs_kernel, dim3(C), dim3(256), 0, st, a);
   return check_launch("bn_act_bwd_coeffs");
 }
 
 extern "C" int ragmi_bn_act_bwd_apply(const void* dy, int64_t dy_bstride, int dy_ch0, const void* x, int64_t x_bstride,
-                                      const void* scale, const void* shift, int relu, const void* c1, const void* c2, const void* c3,
-                                      void* dx, int64_t dx_bstride, int B, int C, int64_t DHW, void* stream) {
+                                      const void* scale, const void* shift, int relu, const void* c0, const void* c1, const void* c2,
+                                      const void* c3, void* dx, int64_t dx_bstride, int B, int C, int64_t DHW, void* stream) {
   using namespace ragmi;
-  RAGMI_REQUIRE(dy && x && scale && shift && c1 && c2 && c3 && dx, RAGMI_EINVAL, "bn_act_bwd_apply: null pointer");
+  RAGMI_REQUIRE(dy && x && scale && shift && c0 && c1 && c2 && c3 && dx, RAGMI_EINVAL, "bn_act_bwd_apply: null pointer");
   RAGMI_REQUIRE(B > 0 && C > 0 && DHW > 0 && B <= 65535 && C <= 65535, RAGMI_EINVAL, "bn_act_bwd_apply: bad size");
   hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3((unsigned)ceil_div(DHW, 1024), C, B), dim3(256), 0, static_cast<hipStream_t>(stream),
                      (const float*)dy, dy_bstride, dy_ch0, (const float*)x, x_bstride, (const float*)scale, (const float*)shift, relu,
-                     (const float*)c1, (const float*)c2, (const float*)c3, (float*)dx, dx_bstride, DHW);
+                     (const float*)c0, (const float*)c1, (const float*)c2, (const float*)c3, (float*)dx, dx_bstride, DHW);
   return check_launch("bn_act_bwd_apply");
 }
 

@@ -1017,6 +1017,19 @@ def _vol(t: torch.Tensor) -> int:
     return n
 
 
+def _planes_overlap(a: torch.Tensor, a_ch0: int, b: torch.Tensor, b_ch0: int, C: int) -> bool:
+    """Do the channels [ch0, ch0 + C) of the dense-plane tensors a and b (same batch and volume) share memory?"""
+    n = C * _vol(a) * 4
+
+    def starts(t, ch0):
+        return t.data_ptr() + ch0 * _vol(t) * 4 + torch.arange(t.shape[0], dtype=torch.int64) * (int(t.stride(0)) * 4)
+    sa, sb = starts(a, a_ch0), starts(b, b_ch0).sort().values
+    k = torch.searchsorted(sb, sa)                                     # sb[k - 1] < sa <= sb[k]
+    after = sb[k.clamp_max(len(sb) - 1)] - sa
+    before = sa - sb[(k - 1).clamp_min(0)]
+    return bool((((k < len(sb)) & (after < n)) | ((k > 0) & (before < n))).any())
+
+
 def bn_train_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: Optional[torch.Tensor],
                    running_var: Optional[torch.Tensor], num_batches_tracked: Optional[torch.Tensor], momentum: float, eps: float):
     """Train-mode BatchNorm statistics of the raw conv output x[B,C,...]: returns the [4, C] tensor (mean, invstd, scale, shift)
@@ -1038,32 +1051,38 @@ def bn_train_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, run
 
 def bn_train_act(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, running_mean: Optional[torch.Tensor],
                  running_var: Optional[torch.Tensor], num_batches_tracked: Optional[torch.Tensor], momentum: float, eps: float, relu: bool,
-                 res: Optional[torch.Tensor] = None):
+                 res: Optional[torch.Tensor] = None, res_ch0: int = 0, out: Optional[torch.Tensor] = None, out_ch0: int = 0):
     """Train-mode BatchNorm + ReLU of the raw conv output x as two launches (ragmi_bn_train_act_fwd): returns (y, stats) with
-    stats the [4, C] tensor (mean, invstd, scale, shift); the running statistics are updated in place.  `res` (same shape) is added
-    after the activation."""
-    _need_gpu(x, gamma, beta, running_mean, running_var, res)
+    stats the [4, C] tensor (mean, invstd, scale, shift); the running statistics are updated in place.  `res` is added after the
+    activation: x's shape, or with `res_ch0` the channels [res_ch0, res_ch0 + C) of a wider buffer.  `out` / `out_ch0`: write y into
+    those channels of a wider buffer (returned as y); they must not overlap x, whose pivots the second launch re-reads."""
+    _need_gpu(x, gamma, beta, running_mean, running_var, res, out)
     B, C = x.shape[:2]
-    if res is not None and tuple(res.shape) != tuple(x.shape):
-        raise ValueError("bn_train_act: res must have the shape of x")
+    for what, t, ch0 in (("res", res, res_ch0), ("out", out, out_ch0)):
+        if t is not None and (t.shape[0] != B or tuple(t.shape[2:]) != tuple(x.shape[2:]) or ch0 < 0 or ch0 + C > t.shape[1]):
+            raise ValueError(f"bn_train_act: {what} must have x's batch and volume and hold channels [{ch0}, {ch0 + C})")
+    if out is not None and _planes_overlap(x, 0, out, out_ch0, C):
+        raise ValueError("bn_train_act: out must not overlap x")
     lib = load_library()
     ws = torch.empty((lib.ragmi_bn_workspace_elems(B, C, _vol(x)),), device=x.device, dtype=torch.float32)
     st = torch.empty((4, C), device=x.device, dtype=torch.float32)
-    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    y = out if out is not None else torch.empty(x.shape, device=x.device, dtype=torch.float32)
     if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
         raise RuntimeError("bn_train_act: num_batches_tracked must be int64")
     p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     check(lib.ragmi_bn_train_act_fwd(x.data_ptr(), _planes(x), B, C, _vol(x), gamma.data_ptr(), beta.data_ptr(), p(running_mean),
                                      p(running_var), p(num_batches_tracked), float(momentum), float(eps), int(relu), ws.data_ptr(),
-                                     st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), st[3].data_ptr(), y.data_ptr(), _planes(y), 0,
-                                     p(res), _planes(res) if res is not None else 0, 0, _stream()), "bn_train_act")
+                                     st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr(), st[3].data_ptr(), y.data_ptr(), _planes(y),
+                                     int(out_ch0), p(res), _planes(res) if res is not None else 0, int(res_ch0), _stream()), "bn_train_act")
     return y, st
 
 
 def bn_act_bwd(dy: torch.Tensor, x: torch.Tensor, scale, shift, relu: bool, mean, invstd, training: bool,
-               out: Optional[torch.Tensor] = None, dgamma_into: Optional[torch.Tensor] = None, dbeta_into: Optional[torch.Tensor] = None):
+               out: Optional[torch.Tensor] = None, dgamma_into: Optional[torch.Tensor] = None, dbeta_into: Optional[torch.Tensor] = None,
+               dy_ch0: int = 0):
     """ReLU + BatchNorm adjoint as two launches (ragmi_bn_act_bwd): returns (dx, dgamma, dbeta); with `dgamma_into` / `dbeta_into`
-    the parameter gradients are accumulated into those tensors and None is returned for them."""
+    the parameter gradients are accumulated into those tensors and None is returned for them.  `dy_ch0`: dy is read from the channels
+    [dy_ch0, dy_ch0 + C) of a wider buffer."""
     _need_gpu(dy, x, scale, shift, mean, invstd, out, dgamma_into, dbeta_into)
     B, C = x.shape[:2]
     lib = load_library()
@@ -1072,7 +1091,7 @@ def bn_act_bwd(dy: torch.Tensor, x: torch.Tensor, scale, shift, relu: bool, mean
     direct = dgamma_into is not None and dbeta_into is not None
     gb = None if direct else torch.empty((2, C), device=x.device, dtype=torch.float32)
     dg, db = (dgamma_into, dbeta_into) if direct else (gb[0], gb[1])
-    check(lib.ragmi_bn_act_bwd(dy.data_ptr(), _planes(dy), 0, x.data_ptr(), _planes(x), scale.data_ptr(), shift.data_ptr(), int(relu),
+    check(lib.ragmi_bn_act_bwd(dy.data_ptr(), _planes(dy), int(dy_ch0), x.data_ptr(), _planes(x), scale.data_ptr(), shift.data_ptr(), int(relu),
                                mean.data_ptr(), invstd.data_ptr(), int(training), B, C, _vol(x), ws.data_ptr(), dx.data_ptr(), _planes(dx),
                                dg.data_ptr(), db.data_ptr(), int(direct), _stream()), "bn_act_bwd")
     return dx, (None if direct else gb[0]), (None if direct else gb[1])
@@ -1093,33 +1112,33 @@ def bn_act(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, relu: bool
 
 def bn_act_bwd_coeffs(dy: torch.Tensor, dy_ch0: int, x: torch.Tensor, scale, shift, relu: bool, mean, invstd, training: bool,
                       dgamma_into: Optional[torch.Tensor] = None, dbeta_into: Optional[torch.Tensor] = None):
-    """Reduction half of the ReLU+BN adjoint: returns the [5, C] tensor (c1, c2, c3, dgamma, dbeta) with
-    dx = g*c1 + x*c2 + c3, g = dy * [x*scale+shift > 0] (ragmi_bn_act_bwd_coeffs).  `dgamma_into` / `dbeta_into`: accumulate the
-    parameter gradients straight into these tensors (a parameter's .grad) instead of rows 3 / 4."""
+    """Reduction half of the ReLU+BN adjoint: returns the [6, C] tensor (c0, c1, c2, c3, dgamma, dbeta) with
+    dx = g*c1 + (x - c0)*c2 + c3, c0 = mean, g = dy * [x*scale+shift > 0] (ragmi_bn_act_bwd_coeffs).  `dgamma_into` / `dbeta_into`:
+    accumulate the parameter gradients straight into these tensors (a parameter's .grad) instead of rows 4 / 5."""
     _need_gpu(dy, x, scale, shift, mean, invstd, dgamma_into, dbeta_into)
     B, C = x.shape[:2]
     lib = load_library()
     ws = torch.empty((lib.ragmi_bn_workspace_elems(B, C, _vol(x)),), device=x.device, dtype=torch.float32)
-    out = torch.empty((5, C), device=x.device, dtype=torch.float32)
+    out = torch.empty((6, C), device=x.device, dtype=torch.float32)
     direct = dgamma_into is not None or dbeta_into is not None
     if direct and (dgamma_into is None or dbeta_into is None):
         raise ValueError("bn_act_bwd_coeffs: pass both dgamma_into and dbeta_into, or neither")
-    dg, db = (dgamma_into, dbeta_into) if direct else (out[3], out[4])
+    dg, db = (dgamma_into, dbeta_into) if direct else (out[4], out[5])
     check(lib.ragmi_bn_act_bwd_coeffs(dy.data_ptr(), _planes(dy), dy_ch0, x.data_ptr(), _planes(x), scale.data_ptr(), shift.data_ptr(),
                                       int(relu), mean.data_ptr(), invstd.data_ptr(), int(training), B, C, _vol(x), ws.data_ptr(),
-                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), dg.data_ptr(), db.data_ptr(), int(direct),
-                                      _stream()), "bn_act_bwd_coeffs")
+                                      out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), dg.data_ptr(), db.data_ptr(),
+                                      int(direct), _stream()), "bn_act_bwd_coeffs")
     return out
 
 
-def bn_act_bwd_apply(dy: torch.Tensor, dy_ch0: int, x: torch.Tensor, scale, shift, relu: bool, c1, c2, c3,
+def bn_act_bwd_apply(dy: torch.Tensor, dy_ch0: int, x: torch.Tensor, scale, shift, relu: bool, c0, c1, c2, c3,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dx = g * c1 + x * c2 + c3 (per channel); `out` may be a channel slice of a wider buffer."""
-    _need_gpu(dy, x, scale, shift, c1, c2, c3, out)
+    """dx = g * c1 + (x - c0) * c2 + c3 (per channel); `out` may be a channel slice of a wider buffer."""
+    _need_gpu(dy, x, scale, shift, c0, c1, c2, c3, out)
     B, C = x.shape[:2]
     dx = out if out is not None else torch.empty(x.shape, device=x.device, dtype=torch.float32)
     check(load_library().ragmi_bn_act_bwd_apply(dy.data_ptr(), _planes(dy), dy_ch0, x.data_ptr(), _planes(x), scale.data_ptr(),
-                                                shift.data_ptr(), int(relu), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), dx.data_ptr(),
+                                                shift.data_ptr(), int(relu), c0.data_ptr(), c1.data_ptr(), c2.data_ptr(), c3.data_ptr(), dx.data_ptr(),
                                                 _planes(dx), B, C, _vol(x), _stream()), "bn_act_bwd_apply")
     return dx
 
