@@ -41,15 +41,17 @@
  *                   it matters only when operands ~2^-25 smaller than their tile's largest carry the sum (measured 1e-3 * sum |w x|
  *                   on operands spread element by element over 2^-20..2^20).  The bound is relative to the sum of |products|, not to
  *                   |y|: cancelling sums lose that many ABSOLUTE digits, as in fp32.  Non-finite inputs give non-finite outputs (an
- *                   Inf may come out as NaN); so do operands above ~2^110 in magnitude, which no scale brings into fp16's range.  Round 2 used bf16 halves (8 bits each, ~2^-17 per product): measured over weight
+ *                   Inf may come out as NaN); so do operands above ~2^110 in magnitude, which no scale brings into fp16's range.  With ReLU a NaN
+ *                   pre-activation is stored as 0 on every route (the epilogues apply fmaxf(u, 0.f)), unlike F.relu, which keeps the NaN.  Round 2 used bf16 halves (8 bits each, ~2^-17 per product): measured over weight
  *                   seeds at the headline size that left the EPE against the CPU reference between 1e-5 and 1.4e-3 px; the fp16
  *                   halves sit on the strict fp32 path's EPE for every seed (tests/test_hip_parity.py::
  *                   test_x3_margin_over_seeds_and_genotypes_at_headline_size).
  *                   Elsewhere (small volumes, a residual input, unsupported channel counts) the call is computed exactly as
- *                   RAGMI_F32.  tests/test_hip_parity.py::test_x3_error_bound_adversarial enforces the bound.
+ *                   RAGMI_F32.  tests/test_hip_parity.py::test_x3_error_bound_adversarial and tests/test_conv3d_k3_sweep.py (every route and form) enforce the bound.
  *      RAGMI_BF16   bf16 activation storage (BASELINE config 3), fp32 on-chip accumulation, BN and tails; the contraction may run
  *                   on the bf16 matrix cores with the (exact) bf16 activations and hi+lo split fp32 weights — an error of
- *                   <= 2^-16 per weight, far below the 2^-8 of the storage format.
+ *                   <= 2^-16 per weight, far below the 2^-8 of the storage format (both halves are rounded to nearest, which leaves
+ *                   <= 2^-18 |w|: the term tests/test_conv3d_k3_sweep.py holds the split-operand kernels to under this storage).
  *    Weights, scale/shift and the final disparity are fp32 in every case.
  */
 #ifndef RAG_AMD_H
@@ -551,6 +553,13 @@ int ragmi_costvol_stem_conv3d_fwd(const void* left, const void* right, const voi
  * dual launch) — there the taps dz != 1 meet only zero padding and only the middle slice of the packed fragments is issued.
  * B never enters: the kernel (hence the rounding) a sample gets does not depend on how a batch is split over ranks.  Always 0 for RAGMI_F32. */
 int ragmi_conv3d_k3_uses_x3(int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int dtype);
+/* Which kernel the same call (with `ntail` full-resolution and `ndown` down-sampling tails of 4 channels) lands on: 0 the depth-1 form
+ * (conv2d_x3_kernel), 1 the deep-level box form (conv3d_x3d_kernel), 2 the z-marching quad-ring form (conv3d_x3q_kernel), 3 the z-marching
+ * form (conv3d_x3_kernel), 4 the fp32-MFMA kernel (conv3d_k3_kernel); RAGMI_EINVAL for arguments no entry point takes.  sched (4 ints, may
+ * be NULL) receives the z-marching work list of routes 2 and 3 — planes per depth segment, segments per column, pairs per group cut into
+ * half items, groups the list is dealt in — and zeros otherwise.  Host code only: no device is touched. */
+int ragmi_conv3d_k3_route(int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int ndown, int dtype,
+                          int32_t* sched);
 
 /* ragmi_conv3d_k3_pack with two options used by the training step: transpose != 0 packs the DATA-GRADIENT conv of a forward
  * weight (source [Cin][Cout][taps], taps flipped), Cout/Cin being those of the packed conv; planar2d != 0: the source is a 2-D

@@ -53,6 +53,7 @@ SIGNATURES = {
                                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int32_p, c_int, c_int, c_tail_p,
                                               c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_conv3d_k3_uses_x3": (c_int, [c_int] * 10),
+    "ragmi_conv3d_k3_route": (c_int, [c_int] * 11 + [c_int32_p]),
     "ragmi_conv3d_k3_g4_caps": (c_int, [c_int] * 10),
     "ragmi_conv3d_k3_quarter_store_supported": (c_int, [c_int] * 10),
     "ragmi_quarter_store_rows": (c_int, [c_int, ctypes.POINTER(ctypes.c_ubyte)]),

@@ -314,6 +314,17 @@ extern "C" int ragmi_conv3d_k3_uses_x3(int Cin, int Cout, int B, int D, int H, i
   return (ragmi::k3_probe(a, Cin, Cout, B, D, H, W, nset, has_res, ntail, 0) && ragmi::k3_route(a, nset, dtype) != ragmi::K3Route::Mfma) ? 1 : 0;
 }
 
+extern "C" int ragmi_conv3d_k3_route(int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int ndown, int dtype,
+                                     int32_t* sched) {
+  using namespace ragmi;
+  for (int i = 0; sched && i < 4; ++i) sched[i] = 0;
+  K3Args a;
+  RAGMI_REQUIRE(k3_probe(a, Cin, Cout, B, D, H, W, nset, has_res, ntail, ndown), RAGMI_EINVAL, "conv3d_k3_route: bad argument");
+  const K3Route route = k3_route(a, nset, dtype);
+  if (sched && (route == K3Route::ZMarch || route == K3Route::QuadRing)) x3_probe_schedule(a, dtype, sched);
+  return (int)route;
+}
+
 extern "C" int ragmi_conv3d_k3_g4_caps(int Cin, int Cout, int B, int D, int H, int W, int nset, int ntail, int ndown, int dtype) {
   ragmi::K3Args a;
   return ragmi::k3_probe(a, Cin, Cout, B, D, H, W, nset, 0, ntail, ndown) ? ragmi::x3_g4_caps(a, nset, dtype) : 0;

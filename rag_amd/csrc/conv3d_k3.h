@@ -640,6 +640,7 @@ bool k3_probe(K3Args& a, int Cin, int Cout, int B, int D, int H, int W, int nset
 int x3_g4_caps(const K3Args& a, int nset, int dtype);      // G4 forms (include/rag_amd.h) the kernel this call lands on takes
 bool x3_quarter_store_ok(K3Args a, int nset, int dtype);      // RAGMI_STORE_QUARTER_ROWS (include/rag_amd.h): the launch this call lands on takes it
 bool quarter_store_rows(int n_in, unsigned char* used);       // the source indices a x0.25 align_corners=True resample reads on one axis
+void x3_probe_schedule(K3Args a, int dtype, int32_t* sched);  // seg_len, nseg, nsplit, ngrp of the z-marching work list (ragmi_conv3d_k3_route)
 struct X3StemSrc;
 // route: K3Route::ZMarch or K3Route::QuadRing, as k3_route answered (a plane source runs on ZMarch)
 int x3_launch(K3Args a, int nset, int dtype, K3Route route, hipStream_t st, const X3StemSrc* src = nullptr);

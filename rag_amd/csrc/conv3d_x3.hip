@@ -1142,6 +1142,14 @@ static void x3_schedule(const K3Args& a, int dtype, int ncog, X3Extra& e) {
   }
 }
 
+// the work list x3_launch would make for the probe launch `a` (k3_probe): sched[0..3] = seg_len, nseg, nsplit, ngrp
+void x3_probe_schedule(K3Args a, int dtype, int32_t* sched) {
+  X3Extra e{};
+  a.tiles_x = (int)ceil_div(a.W, X3_TX); a.tiles_y = (int)ceil_div(a.H, X3_TY);
+  x3_schedule(a, dtype, (a.Cout + 15) / 16, e);
+  sched[0] = e.seg_len; sched[1] = e.nseg; sched[2] = e.nsplit; sched[3] = e.ngrp;
+}
+
 // Quarter store (round 6, include/rag_amd.h RAGMI_STORE_QUARTER_ROWS).  A main output whose only reader is a x0.25 trilinear
 // align_corners=True resample (cell i+2's pre_preprocess two levels down) is read at two source indices per output and axis, and
 // both lie inside the aligned group [4X, 4X + 3]: of every four planes and of every four rows at most two are ever read.  The launch

@@ -1330,6 +1330,20 @@ def conv3d_k3_uses_x3(cin: int, cout: int, B: int, D: int, H: int, W: int, nset:
     return bool(load_library().ragmi_conv3d_k3_uses_x3(cin, cout, B, D, H, W, nset, int(has_res), ntail, _conv_dt(_DT[dtype])))
 
 
+K3_ROUTES = ("Split2d", "Box", "QuadRing", "ZMarch", "Mfma")      # K3Route of rag_amd/csrc/conv3d_k3.h, in order
+
+
+def conv3d_k3_route(cin: int, cout: int, B: int, D: int, H: int, W: int, nset: int = 1, has_res: bool = False, ntail: int = 0,
+                    ndown: int = 0, dtype: torch.dtype = torch.float32):
+    """(route name, (seg_len, nseg, nsplit, ngrp)) of the kernel conv3d_k3 (nset=1) / conv3d_k3_dual (nset=2, cin = both inputs) runs this
+    shape on under the current precision setting; the schedule is zeros off the two z-marching routes.  Needs no GPU."""
+    sched = (ctypes.c_int32 * 4)()
+    r = load_library().ragmi_conv3d_k3_route(cin, cout, B, D, H, W, nset, int(has_res), ntail, ndown, _conv_dt(_DT[dtype]), sched)
+    if r < 0:
+        check(r, "conv3d_k3_route")
+    return K3_ROUTES[r], tuple(sched)
+
+
 def sgd_clip_step(param: torch.Tensor, grad: torch.Tensor, buf: torch.Tensor, lr: float, momentum: float, weight_decay: float,
                   max_norm: float, first_step: bool, workspace: Optional[torch.Tensor] = None,
                   norm_out: Optional[torch.Tensor] = None) -> torch.Tensor:
