@@ -258,6 +258,23 @@ int ragmi_conv3d_k3_plan(int Cout, int B, int D, int H, int W, int nset, int32_t
  * last_6_3d / last_12_3d :270-271): channel mix + folded BN + ReLU, HBM-bound.
  * weight: raw nn.Conv3d weight [Cout, Cin] (1x1x1 squeezed), row-major.
  * Writes y[b, y_ch0 + co, ...].
+ *
+ * Accuracy of the kernels of pointwise.hip, resample.hip, conv2d_strided.hip and of ragmi_cell2d_fwd's staging (enforced per
+ * element against float64 by tests/test_pointwise_resample_sweep.py; mag = sum |w| * |operand|, A = the interpolation of |x| with
+ * the same weights):
+ *   trilinear interpolation               3 * 2^-23 * A                (three nested lerps: one product and one fma rounding each;
+ *                                                                       indices and lambdas are ATen's fp32 rule, common.h)
+ *   1x1x1 fmaf chain over n channels      (n + 1) * 2^-24 * mag
+ *   resample + 1x1x1                      sum_ci |w| * 3 * 2^-23 * A_ci + (Cin + 1) * 2^-24 * sum_ci |w| * A_ci
+ *   strided 3x3 (ragmi_conv2d_k3_strided) (9 Cin + 1) * 2^-24 * mag
+ *   folded BatchNorm                      |scale| * arith + 2^-23 * (|scale * pre| + |shift|); ReLU leaves a bound unchanged
+ *   bf16 storage                          + 2^-8 * |result| per stored tensor
+ *   ragmi_add_fwd                         exact: the correctly rounded sum in the storage type
+ *   ragmi_cell2d_fwd                      s0 / s1 within the resample + 1x1x1 + BatchNorm bound b_s; the 3x3 convolutions within
+ *                                         conv(b_s, |w3|) + the RAGMI_F32X3 bound; then BatchNorm per set and the fp32 sum
+ * The ReLU of all of them is fmaxf(u, 0.f): a NaN pre-activation (a NaN input, Inf - Inf, 0 * Inf) is stored as +0 behind a ReLU,
+ * unlike F.relu, which keeps the NaN; without a ReLU a non-finite input gives non-finite outputs over exactly the outputs whose
+ * taps read it (a zero weight does not shield them: 0 * Inf is NaN, as in ATen).
  */
 int ragmi_conv3d_k1_fwd(const void* x, int64_t x_bstride,
                         const void* weight, const void* scale, const void* shift, int relu,
@@ -560,6 +577,18 @@ int ragmi_conv3d_k3_uses_x3(int Cin, int Cout, int B, int D, int H, int W, int n
  * half items, groups the list is dealt in — and zeros otherwise.  Host code only: no device is touched. */
 int ragmi_conv3d_k3_route(int Cin, int Cout, int B, int D, int H, int W, int nset, int has_res, int ntail, int ndown, int dtype,
                           int32_t* sched);
+/* The same for the 1x1x1 and resample launches (host code only, no device is touched; RAGMI_EINVAL / RAGMI_EUNSUPPORTED as the entry
+ * points themselves).  ragmi_conv3d_k1_plan: the output-channel slab width *nco (24, 16, 12, 8 or 4; Cout runs in ceil(Cout / nco)
+ * slabs) and whether a thread takes four voxels (*vec) in ragmi_conv3d_k1_fwd(_ex); x_align_ok / y_align_ok: the x and y pointers
+ * are aligned to four elements.  ragmi_conv3d_k1_resample_plan: the slab width shared by the n = 1..3 descriptors of
+ * ragmi_conv3d_k1_resample_fwd / _pair_fwd / _multi_fwd; in_sizes holds (Di, Hi, Wi) per descriptor.  ragmi_trilinear3d_route: 1 when
+ * ragmi_trilinear3d_fwd / ragmi_trilinear3d_act_fwd stage their input through LDS (an up-sampling by two or more on every axis),
+ * 0 for the generic gather; the two give the same bits. */
+int ragmi_conv3d_k1_plan(int B, int Cin, int Cout, int64_t DHW, int64_t x_bstride, int64_t y_bstride, int x_align_ok, int y_align_ok,
+                         int dtype, int32_t* nco, int32_t* vec);
+int ragmi_conv3d_k1_resample_plan(int n, const int32_t* Cin, const int32_t* Cout, const int32_t* in_sizes, int B, int Do, int Ho, int Wo,
+                                  int dtype, int32_t* nco);
+int ragmi_trilinear3d_route(int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int align_corners);
 
 /* ragmi_conv3d_k3_pack with two options used by the training step: transpose != 0 packs the DATA-GRADIENT conv of a forward
  * weight (source [Cin][Cout][taps], taps flipped), Cout/Cin being those of the packed conv; planar2d != 0: the source is a 2-D

@@ -323,17 +323,17 @@ static int fill_k1r(K1RArgs& r, const void* x, int64_t x_bstride, int Di, int Hi
   return RAGMI_OK;
 }
 
-template <class T>
-static int launch_k1r(const K1RArgs* r, int n, int B, hipStream_t s) {
-  // slab width (output channels per thread; every slab gathers the input again).  One slab covering all outputs when the
-  // launch has threads to spare or is HBM-bound (>= 128 MB of input: re-reading it costs more than the parallelism buys —
-  // cell 4 at the headline shape: 25.6 us with 16 vs 30.2 with 12); otherwise the widest EVEN split that yields enough threads
-  // (cell 6: 26.0 us with 8 vs 29.9 with 12, whose second slab carries 4 of 16 channels at the full gather cost)
+// slab width (output channels per thread; every slab gathers the input again) of a resample + 1x1x1 launch of n descriptors.  One
+// slab covering all outputs when the launch has threads to spare or is HBM-bound (>= 128 MB of input: re-reading it costs more than
+// the parallelism buys — cell 4 at the headline shape: 25.6 us with 16 vs 30.2 with 12); otherwise the widest EVEN split that
+// yields enough threads (cell 6: 26.0 us with 8 vs 29.9 with 12, whose second slab carries 4 of 16 channels at the full gather
+// cost).  in_sizes: (Di, Hi, Wi) per descriptor.  Host arithmetic only (ragmi_conv3d_k1_resample_plan answers with it).
+static int k1r_plan_nco(int n, const int* Cin, const int* Cout, const int* in_sizes, int B, int Do, int Ho, int Wo, size_t elem_size) {
   int cmax = 0;
-  for (int i = 0; i < n; ++i) cmax = std::max(cmax, r[i].k.Cout);
-  const int64_t threads = (int64_t)B * r[0].Do * r[0].Ho * r[0].Wo * n, want = 256 * 256 * 2;
+  for (int i = 0; i < n; ++i) cmax = std::max(cmax, Cout[i]);
+  const int64_t threads = (int64_t)B * Do * Ho * Wo * n, want = 256 * 256 * 2;
   int64_t in_bytes = 0;
-  for (int i = 0; i < n; ++i) in_bytes += (int64_t)B * r[i].k.Cin * r[i].Di * r[i].Hi * r[i].Wi * (int64_t)sizeof(T);
+  for (int i = 0; i < n; ++i) in_bytes += (int64_t)B * Cin[i] * in_sizes[3 * i] * in_sizes[3 * i + 1] * in_sizes[3 * i + 2] * (int64_t)elem_size;
   static const int widths[5] = {24, 16, 12, 8, 4};
   int cover = 24;
   for (int w : widths)
@@ -345,6 +345,17 @@ static int launch_k1r(const K1RArgs* r, int n, int B, hipStream_t s) {
     for (int w : widths)
       if (w <= cover && (w == cover || cmax % w == 0) && threads * ceil_div(cmax, w) >= want) { nco = w; break; }
   }
+  return nco;
+}
+
+template <class T>
+static int launch_k1r(const K1RArgs* r, int n, int B, hipStream_t s) {
+  int cin[3], cout[3], in_sizes[9];
+  for (int i = 0; i < n; ++i) {
+    cin[i] = r[i].k.Cin; cout[i] = r[i].k.Cout;
+    in_sizes[3 * i] = r[i].Di; in_sizes[3 * i + 1] = r[i].Hi; in_sizes[3 * i + 2] = r[i].Wi;
+  }
+  const int nco = k1r_plan_nco(n, cin, cout, in_sizes, B, r[0].Do, r[0].Ho, r[0].Wo, sizeof(T));
   switch (nco) {
     case 24: launch_k1r_nco<T, 24>(r, n, B, s); break;
     case 16: launch_k1r_nco<T, 16>(r, n, B, s); break;
@@ -384,22 +395,32 @@ static void launch_k1_nco(const K1Args& a, int B, hipStream_t s) {
 // Pick the widest output slab per thread that still leaves enough threads to fill the chip:
 // large volumes read the input once (NCO = Cout); tiny ones (level-12: 53k voxels) are latency-
 // bound, so they trade L2 re-reads of the input for parallelism (slabs of 4 on blockIdx.z).
-template <class T, bool VEC>
-static void launch_k1(const K1Args& a, int B, hipStream_t s) {
-  constexpr int V = VEC ? 4 : 1;
-  const int64_t threads = (int64_t)B * ceil_div(a.dhw, V);
+// Host arithmetic only (ragmi_conv3d_k1_plan answers with these two).
+// 16-B columns need alignment; small volumes use one voxel per thread for 4x the parallelism
+static bool k1_plan_vec(int B, int64_t DHW, int64_t x_bstride, int64_t y_bstride, bool x_align_ok, bool y_align_ok) {
+  return (DHW % 4 == 0) && (x_bstride % 4 == 0) && (y_bstride % 4 == 0) && x_align_ok && y_align_ok && (int64_t)B * DHW >= (1 << 18);
+}
+static int k1_plan_nco(int B, int Cout, int64_t dhw, bool vec) {
+  const int V = vec ? 4 : 1;
+  const int64_t threads = (int64_t)B * ceil_div(dhw, V);
   const int64_t want = 256 * 256 * 4;   // ~4 workgroups per CU (round 4 sweep at the headline shapes: 1.5 per CU +6 us over the small launches, 2 -> 4: -1 us)
   static const int widths[5] = {24, 16, 12, 8, 4};
   int cover = 24;   // smallest slab covering Cout (Cout > 24 runs in slabs of 24)
   for (int w : widths)
-    if (w >= a.Cout) cover = w;
+    if (w >= Cout) cover = w;
   int nco = 4;
   if (threads >= want) {
     nco = cover;    // plenty of threads: read the input once
   } else {
     for (int w : widths)   // widest slab that still yields enough blocks
-      if (w <= cover && threads * ceil_div(a.Cout, w) >= want) { nco = w; break; }
+      if (w <= cover && threads * ceil_div(Cout, w) >= want) { nco = w; break; }
   }
+  return nco;
+}
+
+template <class T, bool VEC>
+static void launch_k1(const K1Args& a, int B, hipStream_t s) {
+  const int nco = k1_plan_nco(B, a.Cout, a.dhw, VEC);
   switch (nco) {
     case 24: launch_k1_nco<T, 24, VEC>(a, B, s); break;
     case 16: launch_k1_nco<T, 16, VEC>(a, B, s); break;
@@ -428,9 +449,7 @@ extern "C" int ragmi_conv3d_k1_fwd_ex(const void* x, int64_t x_bstride, const vo
   RAGMI_REQUIRE(B <= 65535 && Cout <= 4 * 65535 && Cin <= 512, RAGMI_EUNSUPPORTED, "conv3d_k1: B, Cin or Cout too large");
   K1Args a{x, x_bstride, (const float*)weight, (const float*)scale, (const float*)shift,
            y, y_bstride, y_ch0, Cin, Cout, 0, DHW, relu, w_transposed ? 1 : Cin, w_transposed ? Cout : 1};
-  // 16-B columns need alignment; small volumes use one voxel per thread for 4x the parallelism
-  const bool vec = (DHW % 4 == 0) && (x_bstride % 4 == 0) && (y_bstride % 4 == 0) && aligned4(x, dtype) && aligned4(y, dtype) &&
-                   (int64_t)B * DHW >= (1 << 18);
+  const bool vec = k1_plan_vec(B, DHW, x_bstride, y_bstride, aligned4(x, dtype), aligned4(y, dtype));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (dtype == RAGMI_BF16) {
     if (vec) launch_k1<bf16_t, true>(a, B, s); else launch_k1<bf16_t, false>(a, B, s);
@@ -438,6 +457,38 @@ extern "C" int ragmi_conv3d_k1_fwd_ex(const void* x, int64_t x_bstride, const vo
     if (vec) launch_k1<float, true>(a, B, s); else launch_k1<float, false>(a, B, s);
   }
   return check_launch("conv3d_k1");
+}
+
+extern "C" int ragmi_conv3d_k1_plan(int B, int Cin, int Cout, int64_t DHW, int64_t x_bstride, int64_t y_bstride, int x_align_ok,
+                                    int y_align_ok, int dtype, int32_t* nco, int32_t* vec) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && DHW > 0, RAGMI_EINVAL, "conv3d_k1_plan: bad size");
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "conv3d_k1_plan: dtype %d not built", dtype);
+  RAGMI_REQUIRE(B <= 65535 && Cout <= 4 * 65535 && Cin <= 512, RAGMI_EUNSUPPORTED, "conv3d_k1_plan: B, Cin or Cout too large");
+  const bool v = k1_plan_vec(B, DHW, x_bstride, y_bstride, x_align_ok != 0, y_align_ok != 0);
+  if (vec) *vec = v ? 1 : 0;
+  if (nco) *nco = k1_plan_nco(B, Cout, DHW, v);
+  return RAGMI_OK;
+}
+
+extern "C" int ragmi_conv3d_k1_resample_plan(int n, const int32_t* Cin, const int32_t* Cout, const int32_t* in_sizes, int B, int Do,
+                                             int Ho, int Wo, int dtype, int32_t* nco) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(Cin && Cout && in_sizes && n >= 1 && n <= 3, RAGMI_EINVAL, "conv3d_k1_resample_plan: 1..3 descriptors");
+  if (dtype == (RAGMI_BF16 | RAGMI_OUT_F32)) dtype = RAGMI_BF16;      // the slab width follows the INPUT's storage
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "conv3d_k1_resample_plan: dtype %d not built", dtype);
+  RAGMI_REQUIRE(B > 0 && Do > 0 && Ho > 0 && Wo > 0, RAGMI_EINVAL, "conv3d_k1_resample_plan: bad size");
+  int cin[3], cout[3], sz[9];
+  for (int i = 0; i < n; ++i) {
+    RAGMI_REQUIRE(Cin[i] > 0 && Cout[i] > 0 && in_sizes[3 * i] > 0 && in_sizes[3 * i + 1] > 0 && in_sizes[3 * i + 2] > 0, RAGMI_EINVAL,
+                  "conv3d_k1_resample_plan: bad size");
+    RAGMI_REQUIRE(B <= 65535 && (int64_t)in_sizes[3 * i] * in_sizes[3 * i + 1] * in_sizes[3 * i + 2] < (1ll << 31) && Cin[i] <= 512,
+                  RAGMI_EUNSUPPORTED, "conv3d_k1_resample_plan: size too large");
+    cin[i] = Cin[i]; cout[i] = Cout[i];
+    for (int k = 0; k < 3; ++k) sz[3 * i + k] = in_sizes[3 * i + k];
+  }
+  if (nco) *nco = k1r_plan_nco(n, cin, cout, sz, B, Do, Ho, Wo, dtype_size(dtype));
+  return RAGMI_OK;
 }
 
 extern "C" int ragmi_conv3d_k1_chain_supported(int Cin, int Cmid, int Cout) { return (Cin >= 1 && Cin <= 64 && Cmid == 24 && Cout == 12) ? 1 : 0; }

@@ -314,7 +314,22 @@ __global__ __launch_bounds__(256, 2) void trilinear_up_k1_kernel(ResampleK1Args 
   }
 }
 
+// 1: the staged up-sampling kernel (trilinear_up_kernel), 0: the generic gather (trilinear_kernel).  scale <= 0.5 on every axis
+// bounds the input block of a 4 x 8 x 32 output tile by 4 x 6 x 18 (i0 of the last output is at most floor(0.5 * (T - 1)) + 1 past
+// i0 of the first, and i1 one further); 32-bit block count and input offsets.  Host arithmetic only (ragmi_trilinear3d_route).
+static int trilinear_route(int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int align_corners) {
+  const float sd = lin_scale(Di, Do, align_corners), sh = lin_scale(Hi, Ho, align_corners), sw = lin_scale(Wi, Wo, align_corners);
+  const int64_t nblk = ceil_div(Wo, TU_TX) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ);
+  return (sd <= 0.5f && sh <= 0.5f && sw <= 0.5f && nblk < (1ll << 31) && (int64_t)C * Di * Hi * Wi < (1ll << 31)) ? 1 : 0;
+}
+
 }  // namespace ragmi
+
+extern "C" int ragmi_trilinear3d_route(int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int align_corners) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(C > 0 && Di > 0 && Hi > 0 && Wi > 0 && Do > 0 && Ho > 0 && Wo > 0, RAGMI_EINVAL, "trilinear3d_route: non-positive size");
+  return trilinear_route(Di, Hi, Wi, Do, Ho, Wo, C, align_corners);
+}
 
 static int trilinear_launch(const void* x, int64_t x_bstride, void* y, int64_t y_bstride, int y_ch0, int relu, int B, int C, int Di,
                             int Hi, int Wi, int Do, int Ho, int Wo, int align_corners, int dtype, void* stream, const char* what) {
@@ -328,10 +343,8 @@ static int trilinear_launch(const void* x, int64_t x_bstride, void* y, int64_t y
                  lin_scale(Di, Do, align_corners), lin_scale(Hi, Ho, align_corners), lin_scale(Wi, Wo, align_corners),
                  align_corners ? 1 : 0, x_bstride, y_bstride, y_ch0, relu ? 1 : 0};
   const int64_t ovol = (int64_t)Do * Ho * Wo;
-  // scale <= 0.5 on every axis bounds the input block of a 4 x 8 x 32 output tile by 4 x 6 x 18 (i0 of the last output is at most
-  // floor(0.5 * (T - 1)) + 1 past i0 of the first, and i1 one further)
   const int64_t nblk = ceil_div(Wo, TU_TX) * ceil_div(Ho, TU_TY) * ceil_div(Do, TU_TZ);
-  if (a.sd <= 0.5f && a.sh <= 0.5f && a.sw <= 0.5f && nblk < (1ll << 31) && (int64_t)C * Di * Hi * Wi < (1ll << 31)) {
+  if (trilinear_route(Di, Hi, Wi, Do, Ho, Wo, C, align_corners)) {
     dim3 ugrid((unsigned)nblk, B);
     if (dtype == RAGMI_BF16) hipLaunchKernelGGL(trilinear_up_kernel<bf16_t>, ugrid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL(trilinear_up_kernel<float>, ugrid, dim3(256), 0, static_cast<hipStream_t>(stream), a);

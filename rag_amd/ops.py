@@ -1344,6 +1344,43 @@ def conv3d_k3_route(cin: int, cout: int, B: int, D: int, H: int, W: int, nset: i
     return K3_ROUTES[r], tuple(sched)
 
 
+def conv3d_k1_plan(B: int, cin: int, cout: int, dhw: int, x_bstride: Optional[int] = None, y_bstride: Optional[int] = None,
+                   x_align_ok: bool = True, y_align_ok: bool = True, dtype: torch.dtype = torch.float32) -> Tuple[int, bool]:
+    """(slab width NCO, four voxels per thread?) of the conv_k1_kernel instantiation conv3d_k1 runs this shape on
+    (ragmi_conv3d_k1_plan); the batch strides default to those of contiguous tensors.  Needs no GPU."""
+    nco, vec = ctypes.c_int32(), ctypes.c_int32()
+    xb = cin * dhw if x_bstride is None else x_bstride
+    yb = cout * dhw if y_bstride is None else y_bstride
+    check(load_library().ragmi_conv3d_k1_plan(int(B), int(cin), int(cout), int(dhw), int(xb), int(yb), int(bool(x_align_ok)),
+                                              int(bool(y_align_ok)), _DT[dtype], ctypes.byref(nco), ctypes.byref(vec)), "conv3d_k1_plan")
+    return nco.value, bool(vec.value)
+
+
+def conv3d_k1_resample_plan(cins: Sequence[int], couts: Sequence[int], in_sizes: Sequence[Sequence[int]], B: int, size: Sequence[int],
+                            dtype: torch.dtype = torch.float32) -> int:
+    """Slab width NCO of the conv_k1_resample_kernel instantiation that conv3d_k1_resample / _pair / _multi run these 1..3
+    descriptors on (ragmi_conv3d_k1_resample_plan); in_sizes: (Di, Hi, Wi) per descriptor, dtype: the inputs'.  Needs no GPU."""
+    n = len(cins)
+    if not (len(couts) == n and len(in_sizes) == n):
+        raise ValueError("conv3d_k1_resample_plan: one Cin, Cout and input size per descriptor")
+    nco = ctypes.c_int32()
+    Do, Ho, Wo = [int(v) for v in size]
+    check(load_library().ragmi_conv3d_k1_resample_plan(n, _i32_array(cins), _i32_array(couts), _i32_array([v for s in in_sizes for v in s]),
+                                                       int(B), Do, Ho, Wo, _DT[dtype], ctypes.byref(nco)), "conv3d_k1_resample_plan")
+    return nco.value
+
+
+TRILINEAR_ROUTES = ("Generic", "Staged")      # trilinear_kernel / trilinear_up_kernel of rag_amd/csrc/resample.hip
+
+
+def trilinear3d_route(in_size: Sequence[int], size: Sequence[int], channels: int, align_corners: bool) -> str:
+    """The kernel trilinear3d / trilinear3d_act run this resample on (ragmi_trilinear3d_route).  Needs no GPU."""
+    r = load_library().ragmi_trilinear3d_route(*[int(v) for v in in_size], *[int(v) for v in size], int(channels), int(bool(align_corners)))
+    if r < 0:
+        check(r, "trilinear3d_route")
+    return TRILINEAR_ROUTES[r]
+
+
 def sgd_clip_step(param: torch.Tensor, grad: torch.Tensor, buf: torch.Tensor, lr: float, momentum: float, weight_decay: float,
                   max_norm: float, first_step: bool, workspace: Optional[torch.Tensor] = None,
                   norm_out: Optional[torch.Tensor] = None) -> torch.Tensor:
