@@ -21,7 +21,7 @@ $(CSRC)/disp.o: CXXFLAGS += -fno-slp-vectorize
 # same for the single-output-channel convolution: 434 v_pk_fma_f32 + 160 v_mov_b32 instead of 864 v_fmac_f32 (packed fp32 issues at the same FLOP rate)
 $(CSRC)/conv3d_c1.o: CXXFLAGS += -fno-slp-vectorize
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/conv3d_k3.h $(CSRC)/conv3d_x3_common.h $(CSRC)/depth_common.h $(CSRC)/disp_common.h $(CSRC)/prep_common.h include/rag_amd.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/rag_amd.h
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -56,6 +56,7 @@ inline bool dtype_ok(int dtype) { return dtype == RAGMI_F32 || dtype == RAGMI_BF
 inline bool conv_dtype_ok(int dtype) { return dtype_ok(dtype) || dtype == RAGMI_F32X3; }
 inline size_t dtype_size(int dtype) { return dtype == RAGMI_BF16 ? 2 : 4; }
 // 4-element vector paths need the pointer aligned to 4 elements
+inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }   // a: a power of two
 inline bool aligned4(const void* p, int dtype) { return (reinterpret_cast<uintptr_t>(p) & (4 * dtype_size(dtype) - 1)) == 0; }
 
 // thread-local last-error text, returned by ragmi_last_error()

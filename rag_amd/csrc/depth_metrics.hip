@@ -4,9 +4,9 @@
 //   n, sum d, sum d^2, sum |gt - est| / gt, sum (gt - est)^2 / gt, sum (gt - est)^2, sum |log10 est - log10 gt|,
 //   and the counts of max(gt/est, est/gt) < 1.25, 1.25^2, 1.25^3
 // (log_rms's (log gt - log est)^2 is d^2, bit for bit).  Per-pixel terms are fp32 like the reference's arrays; the sums are double.
-// Partials are reduced in a fixed order (an LDS tree per workgroup, then a one-workgroup finalize): no atomics, no memset, so the
-// result is bitwise reproducible and the call graph-capturable.  The reference does a boolean gather, a D2H copy and numpy per batch.
-#include "common.h"
+// Partials are reduced in the fixed order of reduce.h (an LDS tree per workgroup, then a one-workgroup finalize).  The reference
+// does a boolean gather, a D2H copy and numpy per batch.
+#include "reduce.h"
 
 namespace ragmi {
 
@@ -38,19 +38,8 @@ __global__ __launch_bounds__(DM_WG) void depth_metrics_kernel(const float* __res
     v[8] += th < 1.5625f ? 1.0 : 0.0;
     v[9] += th < 1.953125f ? 1.0 : 0.0;
   }
-  __shared__ double red[DM_NSUM][DM_WG];
-#pragma unroll
-  for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int s = DM_WG / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < DM_NSUM) slots[(int64_t)blockIdx.x * DM_NSUM + threadIdx.x] = red[threadIdx.x][0];
+  const auto sum = block_tree_sum<DM_WG>(v);
+  if (threadIdx.x < DM_NSUM) slots[(int64_t)blockIdx.x * DM_NSUM + threadIdx.x] = sum[threadIdx.x];
 }
 
 // out = silog_loss, then compute_errors: silog, abs_rel, log10, rms, sq_rel, log_rms, d1, d2, d3
@@ -63,38 +52,22 @@ __global__ __launch_bounds__(DM_WG) void depth_metrics_finalize_kernel(const dou
                                                                        float* __restrict__ out, double* __restrict__ saved,
                                                                        double* __restrict__ meter) {
   double v[DM_NSUM];
-#pragma unroll
-  for (int k = 0; k < DM_NSUM; ++k) v[k] = 0.0;
-  for (int s = threadIdx.x; s < nslots; s += DM_WG) {
-#pragma unroll
-    for (int k = 0; k < DM_NSUM; ++k) v[k] += slots[(int64_t)s * DM_NSUM + k];
-  }
-  __shared__ double red[DM_NSUM][DM_WG];
-#pragma unroll
-  for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int s = DM_WG / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int k = 0; k < DM_NSUM; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  gather_slots<DM_WG>(slots, nslots, v);
+  const auto sum = block_tree_sum<DM_WG>(v);
   if (threadIdx.x == 0) {
-    const double n = red[0][0];                       // 0 masked pixels: every mean is 0/0 = NaN, as numpy's mean of an empty array
-    const double md = red[1][0] / n, md2 = red[2][0] / n;
+    const double n = sum[0];                          // 0 masked pixels: every mean is 0/0 = NaN, as numpy's mean of an empty array
+    const double md = sum[1] / n, md2 = sum[2] / n;
     const double sa = sqrt(md2 - variance_focus * md * md);
     out[0] = (float)(sa * 10.0);
     out[1] = (float)(sqrt(md2 - md * md) * 100.0);
-    out[2] = (float)(red[3][0] / n);
-    out[3] = (float)(red[6][0] / n);
-    out[4] = (float)sqrt(red[5][0] / n);
-    out[5] = (float)(red[4][0] / n);
+    out[2] = (float)(sum[3] / n);
+    out[3] = (float)(sum[6] / n);
+    out[4] = (float)sqrt(sum[5] / n);
+    out[5] = (float)(sum[4] / n);
     out[6] = (float)sqrt(md2);
-    out[7] = (float)(red[7][0] / n);
-    out[8] = (float)(red[8][0] / n);
-    out[9] = (float)(red[9][0] / n);
+    out[7] = (float)(sum[7] / n);
+    out[8] = (float)(sum[8] / n);
+    out[9] = (float)(sum[9] / n);
     if (saved) {
       saved[0] = n;
       saved[1] = md;
@@ -108,12 +81,10 @@ __global__ __launch_bounds__(DM_WG) void depth_metrics_finalize_kernel(const dou
   }
 }
 
-static int depth_metrics_slots(long long n) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 4 * DM_WG), DM_MAXWG)); }
-
 // the two launches of both entry points; `saved` / `meter` null: the finalize kernel stores `out` only
 static int depth_metrics_launch(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10,
                                 void* saved3, void* meter12, void* stream) {
-  const int nslots = depth_metrics_slots(n);
+  const int nslots = grid_stride_slots(n, DM_WG, DM_MAXWG);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(depth_metrics_kernel, dim3((unsigned)nslots), dim3(DM_WG), 0, st, (const float*)est, (const float*)gt, (int64_t)n,
                      (double*)workspace);
@@ -125,8 +96,9 @@ static int depth_metrics_launch(const void* est, const void* gt, long long n, fl
 }  // namespace ragmi
 
 extern "C" int ragmi_depth_metrics_workspace_elems(long long n) {
+  using namespace ragmi;
   if (n <= 0) return 0;
-  return ragmi::depth_metrics_slots(n) * ragmi::DM_NSUM * 2;        // one double (two floats) per partial
+  return grid_stride_slots(n, DM_WG, DM_MAXWG) * DM_NSUM * 2;        // one double (two floats) per partial
 }
 
 extern "C" int ragmi_depth_metrics_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out10,
@@ -135,7 +107,7 @@ extern "C" int ragmi_depth_metrics_fwd(const void* est, const void* gt, long lon
   RAGMI_REQUIRE(est && gt && workspace && out10, RAGMI_EINVAL, "depth_metrics: null pointer");
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "depth_metrics: dtype %d not built (float32 only)", dtype);
   RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "depth_metrics: bad size %lld", n);
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "depth_metrics: workspace not 8-byte aligned");
+  RAGMI_REQUIRE(aligned_to(workspace, 8), RAGMI_EINVAL, "depth_metrics: workspace not 8-byte aligned");
   return depth_metrics_launch(est, gt, n, variance_focus, workspace, out10, nullptr, nullptr, stream);
 }
 
@@ -145,8 +117,8 @@ extern "C" int ragmi_depth_metrics_meter_fwd(const void* est, const void* gt, lo
   RAGMI_REQUIRE(est && gt && workspace && out10, RAGMI_EINVAL, "depth_metrics_meter: null pointer");
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "depth_metrics_meter: dtype %d not built (float32 only)", dtype);
   RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "depth_metrics_meter: bad size %lld", n);
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "depth_metrics_meter: workspace not 8-byte aligned");
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(saved3) & 7) == 0 && (reinterpret_cast<uintptr_t>(meter12) & 7) == 0, RAGMI_EINVAL,
+  RAGMI_REQUIRE(aligned_to(workspace, 8), RAGMI_EINVAL, "depth_metrics_meter: workspace not 8-byte aligned");
+  RAGMI_REQUIRE(aligned_to(saved3, 8) && aligned_to(meter12, 8), RAGMI_EINVAL,
                 "depth_metrics_meter: saved3 / meter12 not 8-byte aligned");
   return depth_metrics_launch(est, gt, n, variance_focus, workspace, out10, saved3, meter12, stream);
 }

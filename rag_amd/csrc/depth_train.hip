@@ -11,14 +11,15 @@
 //      read its y pixel (the align_corners=True upsample's adjoint, again with the forward's weights) and the 3x3 dm window of
 //      each, T_k = sum w dm(q + 1 - k), then dy_c = sum_k w3[c, k] T_k (du = w3^T dm is never formed).  Extra workgroups of
 //      the same launch (one per weight-gradient entry) sum that entry's slots in a fixed order in double and write or add it.
-// The 12-channel du never exists in memory; dm is 1/Cin of it.  No atomics, no memset, no host synchronisation: the results are
-// bitwise reproducible and the call is graph-capturable.  fp32 storage and arithmetic, double partial sums.  DESIGN.md 4.6.
+// The 12-channel du never exists in memory; dm is 1/Cin of it.  Sums follow the fixed-order contract of reduce.h, without host
+// synchronisation.  fp32 storage and arithmetic, double partial sums.  DESIGN.md 4.6.
 //
 // silog loss over the pixels with gt > 0 of the whole batch, d = log est - log gt:
 //   fwd  grid-stride pass, per-thread double sums of n, sum d, sum d^2, LDS tree, slots; a one-workgroup finalize writes
 //        loss = 10 sqrt(A), A = mean d^2 - lambda mean(d)^2, and saved = {n, mean d, sqrt A} (double) for the backward;
 //   bwd  g_i = grad * 10 (d_i - lambda mean d) / (n sqrt(A) est_i) on masked pixels, 0 elsewhere (and everywhere when n = 0).
 #include "depth_common.h"
+#include "reduce.h"
 
 namespace ragmi {
 
@@ -183,24 +184,16 @@ __device__ __forceinline__ void ac_window(int yi, float scale, int out, int& lo,
 
 __global__ __launch_bounds__(DH_THREADS) void depth_head_bwd_dy_kernel(const DepthHeadBwdArgs a) {
   if ((int)blockIdx.x >= a.ndy) {
-    // ---- weight-gradient entry j: its slots in a fixed order (strided per thread, then an LDS tree), in double
-    __shared__ double red[DH_THREADS];
+    // ---- weight-gradient entry j: its slots in the fixed order of reduce.h, in double (the branch is uniform per workgroup)
     const int j = blockIdx.x - a.ndy;
-    const double* p = a.part + (int64_t)j * a.nslots;
-    double acc = 0.0;
-    for (int s = threadIdx.x; s < a.nslots; s += DH_THREADS) acc += p[s];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-#pragma unroll
-    for (int s = DH_THREADS / 2; s > 0; s >>= 1) {
-      if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-      __syncthreads();
-    }
+    double acc[1];
+    gather_slots<DH_THREADS>(a.part + (int64_t)j * a.nslots, a.nslots, acc);
+    const auto sum = block_tree_sum<DH_THREADS>(acc);
     if (threadIdx.x == 0) {
       const int n3 = 9 * a.Cin;
       const int which = j < n3 ? 0 : (j < n3 + 9 ? 1 : 2);
       float* dst = which == 0 ? a.dw3 + j : (which == 1 ? a.dw1 + (j - n3) : a.db1);
-      const float v = (float)red[0];
+      const float v = (float)sum[0];
       *dst = (a.accumulate >> which) & 1 ? *dst + v : v;
     }
     return;
@@ -261,55 +254,27 @@ constexpr int SL_MAXWG = 1024;   // workgroups of the forward pass at most (grid
 
 __global__ __launch_bounds__(SL_WG) void silog_fwd_kernel(const float* __restrict__ est, const float* __restrict__ gt, int64_t n,
                                                           double* __restrict__ slots) {
-  double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+  double v[3] = {0.0, 0.0, 0.0};
   for (int64_t i = (int64_t)blockIdx.x * SL_WG + threadIdx.x; i < n; i += (int64_t)gridDim.x * SL_WG) {
     const float g = gt[i];
     if (!(g > 0.f)) continue;
     const float d = logf(est[i]) - logf(g);
-    v0 += 1.0;
-    v1 += d;
-    v2 += (double)(d * d);
+    v[0] += 1.0;
+    v[1] += d;
+    v[2] += (double)(d * d);
   }
-  __shared__ double red[3][SL_WG];
-  red[0][threadIdx.x] = v0;
-  red[1][threadIdx.x] = v1;
-  red[2][threadIdx.x] = v2;
-  __syncthreads();
-#pragma unroll
-  for (int s = SL_WG / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 3) slots[(int64_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
+  const auto sum = block_tree_sum<SL_WG>(v);
+  if (threadIdx.x < 3) slots[(int64_t)blockIdx.x * 3 + threadIdx.x] = sum[threadIdx.x];
 }
 
 __global__ __launch_bounds__(SL_WG) void silog_finalize_kernel(const double* __restrict__ slots, int nslots, double variance_focus,
                                                                float* __restrict__ out, double* __restrict__ saved) {
-  double v0 = 0.0, v1 = 0.0, v2 = 0.0;
-  for (int s = threadIdx.x; s < nslots; s += SL_WG) {
-    v0 += slots[(int64_t)s * 3];
-    v1 += slots[(int64_t)s * 3 + 1];
-    v2 += slots[(int64_t)s * 3 + 2];
-  }
-  __shared__ double red[3][SL_WG];
-  red[0][threadIdx.x] = v0;
-  red[1][threadIdx.x] = v1;
-  red[2][threadIdx.x] = v2;
-  __syncthreads();
-#pragma unroll
-  for (int s = SL_WG / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  double v[3];
+  gather_slots<SL_WG>(slots, nslots, v);
+  const auto sum = block_tree_sum<SL_WG>(v);
   if (threadIdx.x == 0) {
-    const double n = red[0][0];                        // n = 0: 0/0 = NaN, the reference's mean of an empty selection
-    const double md = red[1][0] / n, md2 = red[2][0] / n;
+    const double n = sum[0];                           // n = 0: 0/0 = NaN, the reference's mean of an empty selection
+    const double md = sum[1] / n, md2 = sum[2] / n;
     const double sa = sqrt(md2 - variance_focus * md * md);
     out[0] = (float)(sa * 10.0);
     saved[0] = n;
@@ -336,8 +301,6 @@ __global__ __launch_bounds__(SL_WG) void silog_bwd_kernel(const float* __restric
   }
 }
 
-static int silog_slots(long long n) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 4 * SL_WG), SL_MAXWG)); }
-
 }  // namespace ragmi
 
 extern "C" int64_t ragmi_depth_head_bwd_workspace_elems(int B, int Cin, int H, int W) {
@@ -356,7 +319,7 @@ extern "C" int ragmi_depth_head_bwd(const void* y, const void* w3, const void* w
   RAGMI_REQUIRE(ragmi_depth_head_supported(Cin, Hi, Wi, H, W, scale, dtype), RAGMI_EUNSUPPORTED,
                 "depth_head_bwd: Cin=%d %dx%d -> %dx%d x%d not built (Cin 1..16, Hi <= H, Wi <= W, scale 1..8)", Cin, Hi, Wi, H, W,
                 scale);
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "depth_head_bwd: workspace not 8-byte aligned");
+  RAGMI_REQUIRE(aligned_to(workspace, 8), RAGMI_EINVAL, "depth_head_bwd: workspace not 8-byte aligned");
   const int64_t nslots = head_bwd_slots(B, H, W);
   const int64_t ndy = ceil_div(Wi, DH_TW) * ceil_div(Hi, DH_TH) * (int64_t)B;
   const int np = 9 * Cin + 10;
@@ -382,7 +345,7 @@ extern "C" int ragmi_depth_head_bwd(const void* y, const void* w3, const void* w
 
 extern "C" int ragmi_silog_loss_workspace_elems(long long n) {
   if (n <= 0) return 0;
-  return ragmi::silog_slots(n) * 3 * 2;                               // three doubles per workgroup
+  return ragmi::grid_stride_slots(n, ragmi::SL_WG, ragmi::SL_MAXWG) * 3 * 2;      // three doubles per workgroup
 }
 
 extern "C" int ragmi_silog_loss_fwd(const void* est, const void* gt, long long n, float variance_focus, void* workspace, void* out,
@@ -391,9 +354,9 @@ extern "C" int ragmi_silog_loss_fwd(const void* est, const void* gt, long long n
   RAGMI_REQUIRE(est && gt && workspace && out && saved, RAGMI_EINVAL, "silog_loss: null pointer");
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "silog_loss: dtype %d not built (float32 only)", dtype);
   RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "silog_loss: bad size %lld", n);
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(saved) & 7) == 0, RAGMI_EINVAL,
+  RAGMI_REQUIRE(aligned_to(workspace, 8) && aligned_to(saved, 8), RAGMI_EINVAL,
                 "silog_loss: workspace / saved not 8-byte aligned");
-  const int nslots = silog_slots(n);
+  const int nslots = grid_stride_slots(n, SL_WG, SL_MAXWG);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(silog_fwd_kernel, dim3((unsigned)nslots), dim3(SL_WG), 0, st, (const float*)est, (const float*)gt, (int64_t)n,
                      (double*)workspace);
@@ -408,7 +371,7 @@ extern "C" int ragmi_silog_loss_bwd(const void* est, const void* gt, long long n
   RAGMI_REQUIRE(est && gt && saved && gout && grad, RAGMI_EINVAL, "silog_loss_bwd: null pointer");
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "silog_loss_bwd: dtype %d not built (float32 only)", dtype);
   RAGMI_REQUIRE(n > 0, RAGMI_EINVAL, "silog_loss_bwd: bad size %lld", n);
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(saved) & 7) == 0, RAGMI_EINVAL, "silog_loss_bwd: saved not 8-byte aligned");
+  RAGMI_REQUIRE(aligned_to(saved, 8), RAGMI_EINVAL, "silog_loss_bwd: saved not 8-byte aligned");
   const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 4 * SL_WG), 2048));
   hipLaunchKernelGGL(silog_bwd_kernel, dim3((unsigned)nb), dim3(SL_WG), 0, static_cast<hipStream_t>(stream), (const float*)est,
                      (const float*)gt, (int64_t)n, variance_focus, (const double*)saved, (const float*)gout, (float*)grad);

@@ -13,6 +13,7 @@
 // walk loops, the softmax step and the tile reduction are written out as in train.hip, because their shared forms measured slower
 // here (profiles/disp_refactor_ab.json).
 #include "disp_common.h"
+#include "reduce.h"
 
 namespace ragmi {
 
@@ -154,8 +155,8 @@ __global__ __launch_bounds__(256) void disp_softargmin_stats_bwd_kernel(DispStat
 // ---------------------------------------------------------------------------------------------------------------
 // Laplace-style NLL over the head's own variance (Kendall & Gal): per masked pixel (0 < gt < maxdisp), with s = variance + var_floor,
 //   l = smooth_l1(est - gt) * rsqrt(s) + 0.5 ln s.
-// Two-level reduction without atomics: workgroup (x, b) writes its four partial sums to slot (b * gridDim.x + x), the finalize
-// workgroup adds the slots in a fixed order in double: the same bits on every run, and nothing to zero beforehand.
+// Two-level reduction in the fixed order of reduce.h: workgroup (x, b) writes its four partial sums to slot (b * gridDim.x + x), the
+// finalize workgroup adds the slots in double.
 constexpr int UNC_N = 4;         // per slot: n_mask, sum l, sum smooth-L1, sum sqrt(s)
 constexpr int UNC_GX = 64;       // at most this many workgroups per image
 
@@ -178,43 +179,20 @@ __global__ __launch_bounds__(256) void uncertainty_loss_kernel(const float* __re
       v[3] += sq;
     }
   }
-  __shared__ float red[4][UNC_N];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < UNC_N; ++k) {
-    float s = v[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < UNC_N)
-    acc[((int64_t)b * gridDim.x + blockIdx.x) * UNC_N + threadIdx.x] =
-        (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+  const auto sum = block_wave_sum(v);
+  if (threadIdx.x < UNC_N) acc[((int64_t)b * gridDim.x + blockIdx.x) * UNC_N + threadIdx.x] = sum[threadIdx.x];
 }
 
 // out[0] = sum l / N, out[1] = masked smooth-L1 mean, out[2] = mean sqrt(s), out[3] = N; an empty mask gives 0 / 0 like stereo_metrics
 __global__ __launch_bounds__(256) void uncertainty_loss_finalize_kernel(const float* __restrict__ acc, int nslots, float* __restrict__ out) {
-  __shared__ double red[256][UNC_N];
-  double v[UNC_N] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nslots; i += 256)
-#pragma unroll
-    for (int k = 0; k < UNC_N; ++k) v[k] += (double)acc[(int64_t)i * UNC_N + k];
-#pragma unroll
-  for (int k = 0; k < UNC_N; ++k) red[threadIdx.x][k] = v[k];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-#pragma unroll
-      for (int k = 0; k < UNC_N; ++k) red[threadIdx.x][k] += red[threadIdx.x + o][k];
-    }
-    __syncthreads();
-  }
+  double v[UNC_N];
+  gather_slots<256>(acc, nslots, v);
+  const auto sum = block_tree_sum<256>(v);
   if (threadIdx.x == 0) {
-    const double n = red[0][0];
-    out[0] = (float)(red[0][1] / n);
-    out[1] = (float)(red[0][2] / n);
-    out[2] = (float)(red[0][3] / n);
+    const double n = sum[0];
+    out[0] = (float)(sum[1] / n);
+    out[1] = (float)(sum[2] / n);
+    out[2] = (float)(sum[3] / n);
     out[3] = (float)n;
   }
 }

@@ -2,7 +2,7 @@
 // accumulators.  Reference: approaches/rag.py:210-211, 418-430 (mask = 0 < gt < max_disp, masked
 // smooth-L1) and utilstool/metrics.py:21-65 (EPE, D1, Thres-tau, each averaged over the images whose mask keeps at
 // least 10 % of the gt > 0 pixels).  The reference does six boolean gathers and six .item() syncs per batch.
-#include "common.h"
+#include "reduce.h"
 
 namespace ragmi {
 
@@ -35,17 +35,8 @@ __global__ __launch_bounds__(256) void stereo_metrics_kernel(const float* __rest
       if (e > 3.f) v[7] += 1.f;
     }
   }
-  __shared__ float red[4][MET_N];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < MET_N; ++k) {
-    float s = v[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < MET_N) atomicAdd(acc + b * MET_N + threadIdx.x, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+  const auto sum = block_wave_sum(v);      // reduce.h; the workgroups of an image are then combined with float atomics (order not fixed)
+  if (threadIdx.x < MET_N) atomicAdd(acc + b * MET_N + threadIdx.x, sum[threadIdx.x]);
 }
 
 // out[0..5] = loss, EPE, D1, Thres1, Thres2, Thres3;  out[6] = number of masked pixels in the batch;  out[7] = images kept

@@ -3,29 +3,25 @@
 // clip_grad_norm_(parameters, 5) then optimizer.step()).  torch's multi-tensor path issues several launches per group of
 // ~500 small tensors (~1.5 ms of a 15 ms step); with every parameter a view of one buffer the update is a single
 // HBM-bound pass: 5 floats of traffic per element (p, g, buf read; p, buf written; g written back clipped).
-#include "common.h"
+#include "reduce.h"
 
 namespace ragmi {
 
 constexpr int SGD_PARTS = 256;
 
-// part[k] = sum of g[i]^2 over the k-th grid-stride slice (fp64 accumulation, fixed order: deterministic).  MASKED: over the
+// part[k] = sum of g[i]^2 over the k-th grid-stride slice (fp64 accumulation, the fixed order of reduce.h).  MASKED: over the
 // elements with active[i] != 0 only (the others add an exact +0.0, so an all-ones mask gives the unmasked sum bit for bit).
 template <bool MASKED>
 __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const float* __restrict__ g, const uint8_t* __restrict__ active, int64_t n,
                                                              double* __restrict__ part) {
-  double s = 0.0;
+  double s[1] = {0.0};
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     if (MASKED && !active[i]) continue;
     const double v = g[i];
-    s += v * v;
+    s[0] += v * v;
   }
-  __shared__ double red[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  const auto sum = block_wave_sum(s);
+  if (threadIdx.x == 0) part[blockIdx.x] = sum[0];
 }
 
 struct SgdArgs {
@@ -47,13 +43,8 @@ struct SgdArgs {
 // buf = 0.9 * 0 + d = d exactly, torch's lazily created momentum buffer.
 template <bool MASKED>
 __global__ __launch_bounds__(256) void sgd_clip_kernel(SgdArgs a) {
-  __shared__ double red[4];
-  double s = a.part[threadIdx.x];          // SGD_PARTS == blockDim.x
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const float total = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+  const double s[1] = {a.part[threadIdx.x]};          // SGD_PARTS == blockDim.x
+  const float total = (float)sqrt(block_wave_sum(s)[0]);
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.norm_out) a.norm_out[0] = total;
   float coef = 1.f;
   if (a.max_norm > 0.f) coef = fminf(a.max_norm / (total + 1e-6f), 1.f);

@@ -13,11 +13,11 @@
 //   color_stats    mean and std-of-column-stds per channel, float64 [B,3,2].  The column sums of u and u^2 are integers, so
 //                  they are accumulated EXACTLY in 64-bit integers (any order gives the same bits): a column's population
 //                  variance is (Hs S2 - S1^2) / (255 Hs)^2 with an exact numerator, and the mean is an exact integer sum
-//                  divided once.  The std over the column stds is the reference's two-pass form in double, reduced in a fixed
-//                  order (strided, then an LDS tree) by one workgroup per sample.  No atomics, no memset.
+//                  divided once.  The std over the column stds is the reference's two-pass form in double, reduced in the
+//                  fixed order of reduce.h (strided, then an LDS tree) by one workgroup per sample.
 //   color_transfer the stand-alone uint8 image of transfer_color (tests, callers that want the image).
-#include "common.h"
 #include "prep_common.h"
+#include "reduce.h"
 
 namespace ragmi {
 
@@ -192,8 +192,6 @@ __global__ __launch_bounds__(PREP_WG) void color_stats_partial_kernel(const uint
 __global__ __launch_bounds__(PREP_WG) void color_stats_finalize_kernel(const unsigned long long* __restrict__ partial, int nch, int Hs,
                                                                        int Ws, double* __restrict__ out) {
 #pragma clang fp contract(off)
-  __shared__ unsigned long long red_i[3][PREP_WG];
-  __shared__ double red_d[3][PREP_WG];
   const int b = blockIdx.x, tid = threadIdx.x, n = 3 * Ws;
   const unsigned long long* pb = partial + (int64_t)b * nch * n * 2;
   const double inv = 1.0 / ((double)Hs * 255.0);
@@ -208,40 +206,25 @@ __global__ __launch_bounds__(PREP_WG) void color_stats_finalize_kernel(const uns
     if (sum1) *sum1 += s1;
     return sqrt((double)((unsigned long long)Hs * s2 - s1 * s1)) * inv;      // Hs * S2 >= S1^2 (Cauchy-Schwarz), exact in 64 bits
   };
-  auto tree_d = [&]() {
-    __syncthreads();
-    for (int s = PREP_WG / 2; s > 0; s >>= 1) {
-      if (tid < s)
-        for (int c = 0; c < 3; ++c) red_d[c][tid] += red_d[c][tid + s];
-      __syncthreads();
-    }
-  };
   unsigned long long t1[3] = {0, 0, 0};
   double sd[3] = {0.0, 0.0, 0.0};
   for (int x = tid; x < Ws; x += PREP_WG)
     for (int c = 0; c < 3; ++c) sd[c] += colstd(x, c, &t1[c]);
-  for (int c = 0; c < 3; ++c) { red_i[c][tid] = t1[c]; red_d[c][tid] = sd[c]; }
-  __syncthreads();
-  for (int s = PREP_WG / 2; s > 0; s >>= 1) {
-    if (tid < s)
-      for (int c = 0; c < 3; ++c) red_i[c][tid] += red_i[c][tid + s];
-    __syncthreads();
-  }
-  tree_d();
+  const auto sum_i = block_tree_sum<PREP_WG>(t1);                     // exact: u64 (reduce.h)
+  const auto sum_s = block_tree_sum<PREP_WG>(sd);
   double m[3];
-  for (int c = 0; c < 3; ++c) m[c] = red_d[c][0] / (double)Ws;        // mean of the column stds
-  __syncthreads();
+  for (int c = 0; c < 3; ++c) m[c] = sum_s[c] / (double)Ws;           // mean of the column stds
+  __syncthreads();                                                    // every thread has read sum_s: the double tree's LDS is refilled below
   for (int c = 0; c < 3; ++c) sd[c] = 0.0;
   for (int x = tid; x < Ws; x += PREP_WG)
     for (int c = 0; c < 3; ++c) {
       const double d = colstd(x, c, nullptr) - m[c];
       sd[c] += d * d;
     }
-  for (int c = 0; c < 3; ++c) red_d[c][tid] = sd[c];
-  tree_d();
+  const auto sum_d = block_tree_sum<PREP_WG>(sd);
   if (tid < 3) {
-    out[(int64_t)b * 6 + 2 * tid] = (double)red_i[tid][0] / ((double)Hs * (double)Ws * 255.0);
-    out[(int64_t)b * 6 + 2 * tid + 1] = sqrt(red_d[tid][0] / (double)Ws);
+    out[(int64_t)b * 6 + 2 * tid] = (double)sum_i[tid] / ((double)Hs * (double)Ws * 255.0);
+    out[(int64_t)b * 6 + 2 * tid + 1] = sqrt(sum_d[tid] / (double)Ws);
   }
 }
 

@@ -12,6 +12,4 @@ __device__ __forceinline__ float normalize_level(int level, float mean, float st
   return (v - mean) / std;
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace ragmi

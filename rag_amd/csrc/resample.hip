@@ -419,7 +419,7 @@ extern "C" int ragmi_trilinear3d_act_k1_xblend_fwd(const void* x, int64_t x_bstr
   RAGMI_REQUIRE(ragmi_trilinear3d_act_k1_xblend_supported(C, 27, Di, Hi, Wi, Do, Ho, Wo, align_corners), RAGMI_EUNSUPPORTED,
                 "trilinear3d_act_k1_xblend: needs 1..%d input channels, an up-sampling by two or more on every axis and by exactly two along x",
                 TK_MAX_C);
-  RAGMI_REQUIRE(q_bstride % 2 == 0 && reinterpret_cast<uintptr_t>(q) % 8 == 0, RAGMI_EUNSUPPORTED,
+  RAGMI_REQUIRE(q_bstride % 2 == 0 && aligned_to(q, 8), RAGMI_EUNSUPPORTED,
                 "trilinear3d_act_k1_xblend: output rows must be 8-byte aligned");
   ResampleK1Args ka{};
   ka.r = ResampleArgs{x, q, C, Di, Hi, Wi, Do, Ho, Wo,

@@ -4,9 +4,9 @@
 // grid_samples, five avg_pool2d and a few dozen element-wise ATen ops (and their backward), and its warp() makes host tensors and
 // copies them to the device at every call.  Here one thread owns one non-overlapping 3x3 SSIM block (avg_pool2d(kernel_size=3)
 // strides by 3) for all channels and computes, in the same pass, its share of the three sums and the gradient of the total at its
-// own pixels; a second one-workgroup kernel folds the per-workgroup partials in a fixed order.  No atomics, no memset, no host
-// synchronisation: the call is bitwise reproducible and graph-capturable.  DESIGN.md section 4.5.
-#include "common.h"
+// own pixels; a second one-workgroup kernel folds the per-workgroup partials, in the fixed order of reduce.h and without host
+// synchronisation.  DESIGN.md section 4.5.
+#include "reduce.h"
 
 namespace ragmi {
 
@@ -200,45 +200,20 @@ __global__ __launch_bounds__(SS_WG) void selfsup_loss_kernel(SelfSupArgs a, doub
       }
     }
   }
-  // ---- per-workgroup partials: a fixed LDS tree in double, one slot per workgroup
-  __shared__ double red[SS_PART][SS_WG];
-  red[0][threadIdx.x] = acc_ssim;
-  red[1][threadIdx.x] = acc_l1;
-  red[2][threadIdx.x] = acc_sm;
-  __syncthreads();
-#pragma unroll
-  for (int s = SS_WG / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int q = 0; q < SS_PART; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < SS_PART) slots[(int64_t)blockIdx.x * SS_PART + threadIdx.x] = red[threadIdx.x][0];
+  // ---- per-workgroup partials in double, one slot per workgroup
+  const double v[SS_PART] = {acc_ssim, acc_l1, acc_sm};
+  const auto sum = block_tree_sum<SS_WG>(v);
+  if (threadIdx.x < SS_PART) slots[(int64_t)blockIdx.x * SS_PART + threadIdx.x] = sum[threadIdx.x];
 }
 
 // out[0..3] = total, SSIM_mean, L1_mean, smoothness_mean (total = 0.85 SSIM + 0.15 L1 + 0.1 smoothness): the slots in a fixed order
 __global__ __launch_bounds__(SS_FIN) void selfsup_loss_finalize_kernel(const double* __restrict__ slots, int64_t nslots, double inv_ssim,
                                                                        double inv_l1, double inv_sm, float* __restrict__ out) {
-  double v[SS_PART] = {0.0, 0.0, 0.0};
-  for (int64_t s = threadIdx.x; s < nslots; s += SS_FIN) {
-#pragma unroll
-    for (int q = 0; q < SS_PART; ++q) v[q] += slots[s * SS_PART + q];
-  }
-  __shared__ double red[SS_PART][SS_FIN];
-#pragma unroll
-  for (int q = 0; q < SS_PART; ++q) red[q][threadIdx.x] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int s = SS_FIN / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-#pragma unroll
-      for (int q = 0; q < SS_PART; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  double v[SS_PART];
+  gather_slots<SS_FIN>(slots, nslots, v);
+  const auto sum = block_tree_sum<SS_FIN>(v);
   if (threadIdx.x == 0) {
-    const double ssim = red[0][0] * inv_ssim, l1 = red[1][0] * inv_l1, sm = red[2][0] * inv_sm;
+    const double ssim = sum[0] * inv_ssim, l1 = sum[1] * inv_l1, sm = sum[2] * inv_sm;
     out[0] = (float)(0.85 * ssim + 0.15 * l1 + 0.1 * sm);
     out[1] = (float)ssim;
     out[2] = (float)l1;
@@ -276,7 +251,7 @@ extern "C" int ragmi_selfsup_loss_fwd(const void* left, const void* right, const
   RAGMI_REQUIRE(dtype == RAGMI_F32, RAGMI_EUNSUPPORTED, "selfsup_loss: dtype %d not built (float32 only)", dtype);
   RAGMI_REQUIRE(C >= 1 && C <= 4, RAGMI_EUNSUPPORTED, "selfsup_loss: C = %d not built (1..4)", C);
   RAGMI_REQUIRE(B > 0 && H >= 3 && W >= 3, RAGMI_EINVAL, "selfsup_loss: bad size B=%d H=%d W=%d (H, W >= 3)", B, H, W);
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, RAGMI_EINVAL, "selfsup_loss: workspace not 8-byte aligned");
+  RAGMI_REQUIRE(aligned_to(workspace, 8), RAGMI_EINVAL, "selfsup_loss: workspace not 8-byte aligned");
   const int64_t nslots = selfsup_slots(B, H, W);
   RAGMI_REQUIRE(nslots <= 0xffffffffLL, RAGMI_EINVAL, "selfsup_loss: too many pixels");
   SelfSupArgs a;

@@ -341,8 +341,8 @@ extern "C" int ragmi_sparsification_fwd(const void* disp, const void* unc, const
   RAGMI_REQUIRE(K >= 1 && K <= MAXK, RAGMI_EINVAL, "sparsification: fractions = %d is outside 1..%d", K, MAXK);
   RAGMI_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), RAGMI_EINVAL, "sparsification: H * W must stay below 2^31 (32-bit pixel counts)");
   RAGMI_REQUIRE(maxdisp > 0.f, RAGMI_EINVAL, "sparsification: maxdisp must be positive");
-  RAGMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, RAGMI_EINVAL, "sparsification: workspace must be 16-byte aligned");
-  RAGMI_REQUIRE(!meter || (reinterpret_cast<uintptr_t>(meter) & 7) == 0, RAGMI_EINVAL, "sparsification: meter must be 8-byte aligned");
+  RAGMI_REQUIRE(aligned_to(workspace, 16), RAGMI_EINVAL, "sparsification: workspace must be 16-byte aligned");
+  RAGMI_REQUIRE(!meter || aligned_to(meter, 8), RAGMI_EINVAL, "sparsification: meter must be 8-byte aligned");
   const int64_t hw = (int64_t)H * W;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Layout L(B, K);

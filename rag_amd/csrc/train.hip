@@ -6,14 +6,18 @@
 #include <cstdlib>
 
 #include "disp_common.h"
+#include "reduce.h"
 
 namespace ragmi {
 
 // ---------------------------------------------------------------------------------------------------------------
-// Per-channel reductions are two-level and deterministic: every workgroup writes its partial pair to
+// Per-channel reductions are two-level, under the fixed-order contract of reduce.h: every workgroup writes its partial pair to
 // part[(c * nparts + b * gridDim.x + blockIdx.x) * 2 + {0,1}], a one-workgroup-per-channel kernel then sums the
-// partials in double and does the per-channel arithmetic (no same-address float atomics, no zero-filled buffers,
-// no host-side vector math).
+// partials in double and does the per-channel arithmetic (no host-side vector math).  The two trees below are
+// block_tree_sum<256> / gather_slots written out over two LDS arrays each.  On the helper (one [2][256] array) the BN launches
+// measured 1-2 % slower per call in four of six per-kernel figures and the training step 0.3 % slower, both outside the
+// parent's own spread, in two visits; with this text they are the parent's instructions and lie inside it
+// (profiles/reduce_refactor_ab.json), so they keep this text.
 __device__ __forceinline__ void block_pair_store(float s, float q, float* __restrict__ part, int64_t slot) {
   __shared__ float rs[256], rq[256];
   rs[threadIdx.x] = s; rq[threadIdx.x] = q;
@@ -544,8 +548,7 @@ __global__ __launch_bounds__(256) void conv3d_k3_wgrad_reduce_kernel(const float
   const int64_t stride = (int64_t)CoutP * CinP * 27, off = ((int64_t)co * CinP + ci) * 27 + tap;
   float s = 0.f;
   for (int p = lane; p < nparts; p += 64) s += part[p * stride + off];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (lane == 0) {
     const int k = co / dst.rows_per_dst, r = co % dst.rows_per_dst;
     float* d = dst.p[k] + (dst.planar ? ((int64_t)r * Cin + ci) * 9 + (tap - 9) : ((int64_t)r * Cin + ci) * 27 + tap);
@@ -555,7 +558,7 @@ __global__ __launch_bounds__(256) void conv3d_k3_wgrad_reduce_kernel(const float
 
 // dw[co][ci] += sum_v g[co][v] * x[ci][v]   (1x1x1 conv).  A workgroup owns a 4 (co) x 12 (ci) block of dw and a slab of
 // voxels: each thread keeps the 48 partial sums of its voxels in registers (x and g are each read once per block row /
-// column), the workgroup reduces them (wave shuffles, then LDS across the 4 waves) and flushes 48 float atomics.
+// column), the workgroup reduces them (block_wave_sum, reduce.h) and flushes 48 float atomics.
 constexpr int K1W_CO = 4, K1W_CI = 12;
 __global__ __launch_bounds__(256) void conv3d_k1_wgrad_kernel(const float* __restrict__ x, int64_t x_bstride, const float* __restrict__ g,
                                                               int64_t g_bstride, int g_ch0, float* __restrict__ dw, int Cin, int Cout,
@@ -564,11 +567,9 @@ __global__ __launch_bounds__(256) void conv3d_k1_wgrad_kernel(const float* __res
   const float* pg = g + b * g_bstride + (int64_t)(g_ch0 + co0) * dhw;
   const float* px = x + b * x_bstride + (int64_t)ci0 * dhw;
   const int nco = min(K1W_CO, Cout - co0), nci = min(K1W_CI, Cin - ci0);
-  float acc[K1W_CO][K1W_CI];
+  float acc[K1W_CO * K1W_CI];          // row-major [co][ci], the index the flush below decodes
 #pragma unroll
-  for (int i = 0; i < K1W_CO; ++i)
-#pragma unroll
-    for (int j = 0; j < K1W_CI; ++j) acc[i][j] = 0.f;
+  for (int k = 0; k < K1W_CO * K1W_CI; ++k) acc[k] = 0.f;
   for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < dhw; v += (int64_t)gridDim.x * 256) {
     float gv[K1W_CO], xv[K1W_CI];
 #pragma unroll
@@ -578,24 +579,12 @@ __global__ __launch_bounds__(256) void conv3d_k1_wgrad_kernel(const float* __res
 #pragma unroll
     for (int i = 0; i < K1W_CO; ++i)
 #pragma unroll
-      for (int j = 0; j < K1W_CI; ++j) acc[i][j] = fmaf(gv[i], xv[j], acc[i][j]);
+      for (int j = 0; j < K1W_CI; ++j) acc[i * K1W_CI + j] = fmaf(gv[i], xv[j], acc[i * K1W_CI + j]);
   }
-  __shared__ float red[4][K1W_CO * K1W_CI];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int i = 0; i < K1W_CO; ++i)
-#pragma unroll
-    for (int j = 0; j < K1W_CI; ++j) {
-      float v = acc[i][j];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-      if (lane == 0) red[wave][i * K1W_CI + j] = v;
-    }
-  __syncthreads();
+  const auto sum = block_wave_sum(acc);
   if (threadIdx.x < K1W_CO * K1W_CI) {
     const int i = threadIdx.x / K1W_CI, j = threadIdx.x % K1W_CI;
-    if (i < nco && j < nci)
-      atomicAdd(dw + (int64_t)(co0 + i) * Cin + ci0 + j, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+    if (i < nco && j < nci) atomicAdd(dw + (int64_t)(co0 + i) * Cin + ci0 + j, sum[threadIdx.x]);
   }
 }
 
@@ -862,18 +851,8 @@ __global__ __launch_bounds__(256) void conv2d_strided_wgrad_kernel(const float* 
       if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) acc[t] = fmaf(gv, px[(int64_t)iy * W + ix], acc[t]);
     }
   }
-  __shared__ float red[9][256];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) red[t][threadIdx.x] = acc[t];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t) red[t][threadIdx.x] += red[t][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 9) atomicAdd(dw + (int64_t)blockIdx.y * 9 + threadIdx.x, red[threadIdx.x][0]);
+  const auto sum = block_tree_sum<256>(acc);
+  if (threadIdx.x < 9) atomicAdd(dw + (int64_t)blockIdx.y * 9 + threadIdx.x, sum[threadIdx.x]);
 }
 
 // adjoint of DisparityRegression: dprob[b,d,y,x] = dout[b,y,x] * d
@@ -1063,8 +1042,7 @@ extern "C" int ragmi_conv3d_k3_wgrad(const void* x, int64_t x_bstride, const voi
   WgradPlan p;
   const int rc = wgrad_plan(B, Cin, Cout, D, H, W, p);
   if (rc != RAGMI_OK) return rc;
-  const bool vec = W % 4 == 0 && x_bstride % 4 == 0 && g_bstride % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+  const bool vec = W % 4 == 0 && x_bstride % 4 == 0 && g_bstride % 4 == 0 && aligned_to(x, 16) && aligned_to(g, 16);
   WgradArgs a{(const float*)x, (const float*)g, (float*)workspace, x_bstride, g_bstride, g_ch0, Cin, Cout, D, H, W, p.tx, p.ty, p.tz,
               (int)p.ntiles};
   const dim3 grid(p.gx, p.gy, p.gz), block(192);
