@@ -275,6 +275,22 @@ int ragmi_conv3d_k3_plan(int Cout, int B, int D, int H, int W, int nset, int32_t
  * The ReLU of all of them is fmaxf(u, 0.f): a NaN pre-activation (a NaN input, Inf - Inf, 0 * Inf) is stored as +0 behind a ReLU,
  * unlike F.relu, which keeps the NaN; without a ReLU a non-finite input gives non-finite outputs over exactly the outputs whose
  * taps read it (a zero weight does not shield them: 0 * Inf is NaN, as in ATen).
+ *
+ * Accuracy of the head's kernels — ragmi_conv3d_k3_small_fwd(_ex) on both of its kernels (ragmi_conv3d_k3_small_route),
+ * ragmi_upconv3d_c1_fwd, ragmi_trilinear3d_act_k1_fwd / _xblend_fwd, ragmi_uptaps3d_fwd / _xblended_fwd — in the same vocabulary
+ * (enforced per element against float64 by tests/test_head_kernel_sweep.py; conv(., |w|) = the 3x3x3 convolution with |w|, U = the x2
+ * interpolation with the fp32 index rule):
+ *   small 3x3x3 (VALU form and conv3d_c1)   (27 Cin + 1) * 2^-24 * mag                       (one fmaf chain, as the strided 3x3 line)
+ *   ragmi_upconv3d_c1_fwd                   conv(3 * 2^-23 * A, |w|) + (27 Cin + 1) * 2^-24 * conv(A, |w|)
+ *   ragmi_trilinear3d_act_k1_fwd            the resample + 1x1x1 line: b_P = (3 * 2^-23 + (C + 1) * 2^-24) * sum_c |w| * A_c
+ *   ragmi_trilinear3d_act_k1_xblend_fwd     the same + 9 * 2^-24, of sum_dx shift_dx(U_x(sum_c |w| * A_c))    (the 9-term x chain)
+ *   ragmi_uptaps3d_fwd                      25 * 2^-24 * M, M = sum_t shift_t(U(|P_t|))      (<= 9 roundings along x, 9 along y, 6 along z)
+ *   ragmi_uptaps3d_xblended_fwd             16 * 2^-24 * sum_g shift_g(U_yz(|Q_g|))          (<= 9 along y, 6 along z, the epilogue)
+ *   the tap pair from x                     sum_t shift_t(U(b_P)) + 25 * 2^-24 * sum_t shift_t(U(sum_c |w_t| * A_c))
+ *   folded BatchNorm, ReLU, bf16 storage    the lines above, unchanged; the residual of the small form adds 2^-23 * (|act(u)| + |res|)
+ * ragmi_trilinear3d_act_k1_fwd applies its ReLU before the mix: a NaN sample enters the mix as 0.  Non-finite inputs stay local as
+ * described above in all of them: uptaps3d_kernel multiplies a window slot only where it belongs to the source pair (i0, i1) of the
+ * row, column or plane, and the convolution's zero padding takes no part.
  */
 int ragmi_conv3d_k1_fwd(const void* x, int64_t x_bstride,
                         const void* weight, const void* scale, const void* shift, int relu,
@@ -589,6 +605,13 @@ int ragmi_conv3d_k1_plan(int B, int Cin, int Cout, int64_t DHW, int64_t x_bstrid
 int ragmi_conv3d_k1_resample_plan(int n, const int32_t* Cin, const int32_t* Cout, const int32_t* in_sizes, int B, int Do, int Ho, int Wo,
                                   int dtype, int32_t* nco);
 int ragmi_trilinear3d_route(int Di, int Hi, int Wi, int Do, int Ho, int Wo, int C, int align_corners);
+/* Which kernel ragmi_conv3d_k3_small_fwd_ex runs this call on, decided by the code the launch itself calls (host code only, no device
+ * is touched; RAGMI_EINVAL / RAGMI_EUNSUPPORTED as the entry point itself): 0 the single-output-channel z-marching kernel
+ * conv3d_c1_kernel (Cout == 1, no residual, Cin <= 64, W % 4 == 0, >= 2^18 voxels PER SAMPLE, batch strides that are multiples of
+ * four elements and x / y pointers aligned to four elements: x_align_ok / y_align_ok), else 1 + cfg: conv3d_k3_kernel<.., VALU> on
+ * tile configuration cfg of ragmi_conv3d_k3_plan's table (0: 32 x 8 x 4 voxels, 1: 16 x 8 x 4, 2: 8 x 8 x 4). */
+int ragmi_conv3d_k3_small_route(int Cin, int Cout, int B, int D, int H, int W, int dtype, int y_dtype, int has_res, int64_t x_bstride,
+                                int64_t y_bstride, int x_align_ok, int y_align_ok);
 
 /* ragmi_conv3d_k3_pack with two options used by the training step: transpose != 0 packs the DATA-GRADIENT conv of a forward
  * weight (source [Cin][Cout][taps], taps flipped), Cout/Cin being those of the packed conv; planar2d != 0: the source is a 2-D

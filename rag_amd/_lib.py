@@ -57,6 +57,7 @@ SIGNATURES = {
     "ragmi_conv3d_k1_plan": (c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int32_p, c_int32_p]),
     "ragmi_conv3d_k1_resample_plan": (c_int, [c_int, c_int32_p, c_int32_p, c_int32_p, c_int, c_int, c_int, c_int, c_int, c_int32_p]),
     "ragmi_trilinear3d_route": (c_int, [c_int] * 8),
+    "ragmi_conv3d_k3_small_route": (c_int, [c_int] * 9 + [c_int64, c_int64, c_int, c_int]),
     "ragmi_conv3d_k3_g4_caps": (c_int, [c_int] * 10),
     "ragmi_conv3d_k3_quarter_store_supported": (c_int, [c_int] * 10),
     "ragmi_quarter_store_rows": (c_int, [c_int, ctypes.POINTER(ctypes.c_ubyte)]),

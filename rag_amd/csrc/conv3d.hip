@@ -242,19 +242,32 @@ extern "C" int ragmi_conv3d_k3_small_fwd(const void* x, int64_t x_bstride, const
                                       Cout, D, H, W, dtype, dtype, stream);
 }
 
+// the argument checks ragmi_conv3d_k3_small_fwd_ex and ragmi_conv3d_k3_small_route share
+static int k3_small_check(int Cin, int Cout, int dtype, int y_dtype) {
+  using namespace ragmi;
+  RAGMI_REQUIRE(y_dtype == dtype || (dtype == RAGMI_BF16 && y_dtype == RAGMI_F32), RAGMI_EUNSUPPORTED,
+                "conv3d_k3_small: output dtype %d with input dtype %d not built (same, or fp32 out of bf16)", y_dtype, dtype);
+  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "conv3d_k3_small: dtype %d not built", dtype);
+  RAGMI_REQUIRE(Cout >= 1 && Cout <= 2 && Cin % CK == 0 && (size_t)Cout * Cin * 36 * sizeof(float) <= (size_t)K3_MAX_WLDS_BYTES,
+                RAGMI_EUNSUPPORTED, "conv3d_k3_small: needs Cout <= 2 and Cin a multiple of %d, <= %d (use ragmi_conv3d_k3_fwd otherwise)",
+                CK, K3_MAX_WLDS_BYTES / (2 * 36 * 4));
+  return RAGMI_OK;
+}
+
+// which kernel ragmi_conv3d_k3_small_fwd_ex runs `a` on: 0 conv3d_c1_kernel, 1 + cfg conv3d_k3_kernel<.., VALU> on tile configuration cfg
+static int k3_small_route(const ragmi::K3Args& a, bool x_aligned, bool y_aligned) {
+  return ragmi::c1_eligible(a, x_aligned, y_aligned) ? 0 : 1 + ragmi::choose_cfg(a.B, a.D, a.H, a.W);
+}
+
 extern "C" int ragmi_conv3d_k3_small_fwd_ex(const void* x, int64_t x_bstride, const void* weight, const void* scale,
                                             const void* shift, int relu, void* y, int64_t y_bstride, int y_ch0,
                                             const void* res, int64_t res_bstride, int res_ch0, int B, int Cin, int Cout,
                                             int D, int H, int W, int dtype, int y_dtype, void* stream) {
   using namespace ragmi;
-  RAGMI_REQUIRE(y_dtype == dtype || (dtype == RAGMI_BF16 && y_dtype == RAGMI_F32), RAGMI_EUNSUPPORTED,
-                "conv3d_k3_small: output dtype %d with input dtype %d not built (same, or fp32 out of bf16)", y_dtype, dtype);
   RAGMI_REQUIRE(x && weight && y, RAGMI_EINVAL, "conv3d_k3_small: null pointer");
   RAGMI_REQUIRE((scale == nullptr) == (shift == nullptr), RAGMI_EINVAL, "conv3d_k3_small: scale/shift must both be given or both NULL");
-  RAGMI_REQUIRE(dtype_ok(dtype), RAGMI_EUNSUPPORTED, "conv3d_k3_small: dtype %d not built", dtype);
-  RAGMI_REQUIRE(Cout >= 1 && Cout <= 2 && Cin % CK == 0 && (size_t)Cout * Cin * 36 * sizeof(float) <= (size_t)K3_MAX_WLDS_BYTES,
-                RAGMI_EUNSUPPORTED, "conv3d_k3_small: needs Cout <= 2 and Cin a multiple of %d, <= %d (use ragmi_conv3d_k3_fwd otherwise)",
-                CK, K3_MAX_WLDS_BYTES / (2 * 36 * 4));
+  const int ok = k3_small_check(Cin, Cout, dtype, y_dtype);
+  if (ok != RAGMI_OK) return ok;
   K3Args a{};
   const int32_t ych = y_ch0, rch = res_ch0;
   const int rc = fill_common(a, x, x_bstride, y, y_bstride, &ych, res, res_bstride, &rch, B, Cin, Cout, D, H, W, relu);
@@ -262,10 +275,24 @@ extern "C" int ragmi_conv3d_k3_small_fwd_ex(const void* x, int64_t x_bstride, co
   a.wp[0] = (const float*)weight; a.scale[0] = (const float*)scale; a.shift[0] = (const float*)shift;
   a.nchunks[0] = Cin / CK;
   a.store_main = 1;
-  if (c1_eligible(a, dtype, y_dtype)) return c1_launch(a, dtype, y_dtype, static_cast<hipStream_t>(stream));     // conv3d_c1.hip
-  if (dtype == RAGMI_BF16 && y_dtype == RAGMI_F32) return launch_k3_valu_bf16_f32out(a, choose_cfg(B, D, H, W), static_cast<hipStream_t>(stream));
-  return dtype == RAGMI_BF16 ? launch_k3_valu_bf16(a, choose_cfg(B, D, H, W), static_cast<hipStream_t>(stream))
-                             : launch_k3_valu_f32(a, choose_cfg(B, D, H, W), static_cast<hipStream_t>(stream));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int route = k3_small_route(a, aligned4(x, dtype), aligned4(y, y_dtype));
+  if (route == 0) return c1_launch(a, dtype, y_dtype, st);     // conv3d_c1.hip
+  if (dtype == RAGMI_BF16 && y_dtype == RAGMI_F32) return launch_k3_valu_bf16_f32out(a, route - 1, st);
+  return dtype == RAGMI_BF16 ? launch_k3_valu_bf16(a, route - 1, st) : launch_k3_valu_f32(a, route - 1, st);
+}
+
+extern "C" int ragmi_conv3d_k3_small_route(int Cin, int Cout, int B, int D, int H, int W, int dtype, int y_dtype, int has_res,
+                                           int64_t x_bstride, int64_t y_bstride, int x_align_ok, int y_align_ok) {
+  using namespace ragmi;
+  const int ok = k3_small_check(Cin, Cout, dtype, y_dtype);
+  if (ok != RAGMI_OK) return ok;
+  K3Args a{};
+  const int32_t ch0 = 0;
+  const void* const some = &a;      // (x, y and res are only ever compared with null here)
+  const int rc = fill_common(a, some, x_bstride, &a, y_bstride, &ch0, has_res ? some : nullptr, x_bstride, &ch0, B, Cin, Cout, D, H, W, 0);
+  if (rc != RAGMI_OK) return rc;
+  return k3_small_route(a, x_align_ok != 0, y_align_ok != 0);
 }
 
 extern "C" int ragmi_conv3d_k3_dual_fwd(const void* x, int64_t x_bstride, int CinA, const void* packedA,

@@ -411,7 +411,9 @@ static int upconv_launch_typed(CUArgs a, hipStream_t st) {
 // output planes.  Nesting is therefore x, y, z (ATen's).
 // Every blend is written as weights over the thread's level-6 window (4 columns, 3 rows, UT_PZ planes) built from lin_index per
 // thread — a source pair that starts one lower than the x2 pattern (the last output of an axis in fp32) just moves its two weights
-// one slot down; positions outside the upsampled volume (the convolution's zero padding) get zero weights.
+// one slot down; positions outside the upsampled volume (the convolution's zero padding) get zero weights.  A slot outside a source
+// pair, or a position outside the volume, is not multiplied where that can be helped without a cost (0 * Inf is NaN): the spare slot
+// of the x2 pattern is skipped wave-uniformly and the padding's terms are taken back in the waves that have any.
 // Frame as upconv3d_c1_kernel: 64 x 32 tile, 4 output planes, XCD-aware tile order; a stage is the THREE level-6 blocks of one
 // (dz, dy) (30 KB), double-buffered in LDS: the next stage's loads travel under this stage's arithmetic.
 constexpr int UT_TY = 64, UT_TX = 32, UT_THREADS = 256, UT_ZSEG = 4, UT_TAPS = 27;
@@ -503,39 +505,61 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
   };
   // y: upsampled rows gy = y0 + 2ty - 1 + r, r = 0 .. 3 (2 output rows + halo), over block rows ty .. ty+2 (slots 0 .. 2).  The x2
   // pattern puts r = 0, 1 on slots (0, 1) and r = 2, 3 on (1, 2), or one lower: (0, 1)
+  // A term is multiplied only where the slot belongs to the row's source pair (i0, i1) — whatever its weight, as in ATen — and the row
+  // is inside the volume: 0 * Inf is NaN, so a slot that merely carries a zero weight must not meet a non-finite value.  iny[r]: the
+  // row is inside; ys0[r]: slot 0 belongs to its pair (r >= 2: only where the pair sits one lower)
   float wy[4][3];
+  bool iny[4], ys0[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int gy = y0 + 2 * ty - 1 + r, base = py0 + ty;
     const LinIdx l = lin_index(min(max(gy, 0), H - 1), a.Hi, H, a.sh, 1);
     const bool in = (unsigned)gy < (unsigned)H;
+    iny[r] = in;
+    ys0[r] = in && (l.i0 == base || l.i1 == base);
 #pragma unroll
     for (int s = 0; s < 3; ++s) wy[r][s] = in ? (l.i0 - base == s ? l.w0 : 0.f) + (l.i1 - base == s ? l.w1 : 0.f) : 0.f;
   }
   // x: upsampled columns gx = x0 + 4tx - 1 + u, u = 0 .. 5 (4 outputs + halo), over block columns 2tx .. 2tx+3 (slots 0 .. 3):
   // u = 0, 1 on slots (0, 1); u = 2, 3 on (1, 2) or one lower; u = 4, 5 on (2, 3) or one lower.  wx[u][j]: slot xs(u) + j
+  // inx0 / inx5: the halo columns u = 0 and u = 5 are inside the row (u = 1 .. 4 are the thread's own outputs); low_x: slot 0 of
+  // some u >= 2 belongs to the pair of some lane of the wave (the pair sits one lower) — otherwise those terms are skipped
+  // (wave-uniform)
   float wx[6][3];
+  bool inx0 = true, inx5 = true, low_x = false;
 #pragma unroll
   for (int u = 0; u < 6; ++u) {
     const int gx = x0 + 4 * tx - 1 + u, base = px0 + 2 * tx + (u >= 4 ? 1 : 0);
     const LinIdx l = lin_index(min(max(gx, 0), W - 1), a.Wi, W, a.sw, 1);
     const bool in = (unsigned)gx < (unsigned)W;
+    if (u == 0) inx0 = in;
+    if (u == 5) inx5 = in;
+    if (u >= 2) low_x = low_x || __any(in && (l.i0 == base || l.i1 == base));
 #pragma unroll
     for (int s = 0; s < 3; ++s) wx[u][s] = in ? (l.i0 - base == s ? l.w0 : 0.f) + (l.i1 - base == s ? l.w1 : 0.f) : 0.f;
   }
-  // the block's first row enters the dy = 2 taps only where a row pair sits one lower (wave-uniform skip otherwise)
-  const bool row0_dy2 = __any(wy[2][0] != 0.f || wy[3][0] != 0.f);
+  // the block's first row enters the rows r = 2, 3 (the dy = 2 taps, and output row 1 of dy = 1) only where a row pair sits one lower
+  // (wave-uniform skips otherwise)
+  const bool row0_r2 = __any(ys0[2]), row0_dy2 = __any(ys0[2] || ys0[3]);
+  // some lane's halo row r = 0 / r = 3 is outside the volume (the first / last rows of it only: wave-uniform)
+  const bool edge_r0 = __any(!iny[0]), edge_r3 = __any(!iny[3]);
   // z (wave-uniform): upsampled plane z = zs - 1 + zi over block planes 0 .. UT_PZ-1; planes outside the volume or past the
   // segment's last output plane + 1 contribute nothing
+  // lz(zi, p), one bit each of a wave-uniform mask: block plane p belongs to the plane's source pair (a weight of zero still
+  // multiplies, as above)
   float wz[NP][UT_PZ];
+  unsigned lzm = 0;
+  auto lz = [&](int zi, int p) { return ((lzm >> (zi * UT_PZ + p)) & 1u) != 0; };
 #pragma unroll
   for (int zi = 0; zi < NP; ++zi) {
     const int z = zs - 1 + zi;
     const bool live = z >= 0 && z <= min(ze, D - 1);
     const LinIdx l = lin_index(min(max(z, 0), D - 1), a.Di, D, a.sd, 1);
 #pragma unroll
-    for (int p = 0; p < UT_PZ; ++p)
+    for (int p = 0; p < UT_PZ; ++p) {
+      if (live && (l.i0 - pz0 == p || l.i1 - pz0 == p)) lzm |= 1u << (zi * UT_PZ + p);
       wz[zi][p] = live ? (l.i0 - pz0 == p ? l.w0 : 0.f) + (l.i1 - pz0 == p ? l.w1 : 0.f) : 0.f;
+    }
   }
   float acc[ZSEG][2][4];
 #pragma unroll
@@ -556,7 +580,7 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
     for (int p = 0; p < UT_PZ; ++p) {
       need[p] = false;
 #pragma unroll
-      for (int k = 0; k < ZSEG; ++k) need[p] = need[p] || (zs + k < ze && wz[k + dz][p] != 0.f);
+      for (int k = 0; k < ZSEG; ++k) need[p] = need[p] || (zs + k < ze && lz(k + dz, p));
     }
     float R[UT_PZ][2][4];                                   // sum over dy, dx of the taps of this dz, blended along x and y
 #pragma unroll
@@ -569,6 +593,15 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
       constexpr int dy = decltype(dy_)::value, g = dz * 3 + dy;
       const float* const cur = blk[g & 1];
       if constexpr (g + 1 < 9) prefetch(g + 1);
+      // rows outside the volume (r = 0 above it: the dy = 0 terms of output row 0, which starts at zero; r = 3 below it: the dy = 2
+      // terms of output row 1) are the convolution's zero padding: their terms are taken back where a wave has such a row
+      float keep[UT_PZ][4];
+      if (dy == 2 && edge_r3) {
+#pragma unroll
+        for (int p = 0; p < UT_PZ; ++p)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) keep[p][i] = R[p][1][i];
+      }
       static_for<UT_PZ>([&](auto p_) {
         constexpr int p = decltype(p_)::value;
         if (need[p]) {
@@ -580,25 +613,39 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
                 if constexpr (XB) {
                   const float4 v = *reinterpret_cast<const float4*>(cur + (p * UT_PY + ty + s) * UT_TX + 4 * tx);
                   Q[0] = v.x; Q[1] = v.y; Q[2] = v.z; Q[3] = v.w;
-                }
+                } else {
+                  auto xstage = [&](auto low_) {
+                    constexpr bool LOW = decltype(low_)::value;      // slot 0 of the columns u >= 2 takes part
 #pragma unroll
-                for (int dx = 0; dx < (XB ? 0 : 3); ++dx) {
-                  const float* const q = cur + dx * UT_BLK + p * UT_PLANE + s * UT_RS + wbase;
-                  const float2 v0 = *reinterpret_cast<const float2*>(q), v1 = *reinterpret_cast<const float2*>(q + 2);
-                  const float v[4] = {v0.x, v0.y, v1.x, v1.y};
+                    for (int dx = 0; dx < 3; ++dx) {
+                      const float* const q = cur + dx * UT_BLK + p * UT_PLANE + s * UT_RS + wbase;
+                      const float2 v0 = *reinterpret_cast<const float2*>(q), v1 = *reinterpret_cast<const float2*>(q + 2);
+                      const float v[4] = {v0.x, v0.y, v1.x, v1.y};
 #pragma unroll
-                  for (int i = 0; i < 4; ++i) {
-                    const int u = i + dx, xs = u >= 4 ? 1 : 0;       // compile time
-                    float qv = dx == 0 ? wx[u][0] * v[xs] : fmaf(wx[u][0], v[xs], Q[i]);
-                    qv = fmaf(wx[u][1], v[xs + 1], qv);
-                    if (u >= 2) qv = fmaf(wx[u][2], v[xs + 2], qv);
-                    Q[i] = qv;
-                  }
+                      for (int i = 0; i < 4; ++i) {
+                        const int u = i + dx, xs = u >= 4 ? 1 : 0;       // compile time
+                        float qv;
+                        if (u < 2 || LOW) {
+                          qv = dx == 0 ? wx[u][0] * v[xs] : fmaf(wx[u][0], v[xs], Q[i]);
+                          qv = fmaf(wx[u][1], v[xs + 1], qv);
+                        } else {
+                          qv = dx == 0 ? wx[u][1] * v[xs + 1] : fmaf(wx[u][1], v[xs + 1], Q[i]);
+                        }
+                        if (u >= 2) qv = fmaf(wx[u][2], v[xs + 2], qv);
+                        // a halo column outside the row is the convolution's zero padding: its term is not taken
+                        if (u == 0) qv = inx0 ? qv : 0.f;
+                        if (u == 5) qv = inx5 ? qv : Q[i];
+                        Q[i] = qv;
+                      }
+                    }
+                  };
+                  if (low_x) xstage(std::true_type{}); else xstage(std::false_type{});
                 }
 #pragma unroll
                 for (int ro = 0; ro < 2; ++ro) {
                   const int r = ro + dy;
                   if (r < 2 && s == 2) continue;
+                  if (r == 2 && s == 0 && !row0_r2) continue;
 #pragma unroll
                   for (int i = 0; i < 4; ++i) R[p][ro][i] = fmaf(wy[r][s], Q[i], R[p][ro][i]);
                 }
@@ -607,6 +654,18 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
           });
         }
       });
+      if (dy == 0 && edge_r0) {
+#pragma unroll
+        for (int p = 0; p < UT_PZ; ++p)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) R[p][0][i] = iny[0] ? R[p][0][i] : 0.f;
+      }
+      if (dy == 2 && edge_r3) {
+#pragma unroll
+        for (int p = 0; p < UT_PZ; ++p)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) R[p][1][i] = iny[3] ? R[p][1][i] : keep[p][i];
+      }
       if constexpr (g + 1 < 9) commit(blk[(g + 1) & 1]);     // (the buffer stage g - 1 read: every thread left it before the last barrier)
       __syncthreads();
     });
@@ -615,7 +674,7 @@ __global__ __launch_bounds__(UT_THREADS, 2) void uptaps3d_kernel(UTArgs a) {
 #pragma unroll
       for (int k = 0; k < ZSEG; ++k) {
         const float wk = wz[k + dz][p];
-        if (zs + k < ze && wk != 0.f) {
+        if (zs + k < ze && lz(k + dz, p)) {
 #pragma unroll
           for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -727,7 +786,8 @@ extern "C" int ragmi_upconv3d_c1_fwd(const void* x, int64_t x_bstride, const voi
 namespace ragmi {
 
 // Cout == 1, no residual input, rows of whole 16-byte elements (W % 4 == 0 and aligned bases), volumes big enough to fill the chip
-bool c1_eligible(const K3Args& a, int dtype, int y_dtype) {
+// (x_aligned / y_aligned: the x and y pointers sit on four elements — the launch measures them, ragmi_conv3d_k3_small_route is told)
+bool c1_eligible(const K3Args& a, bool x_aligned, bool y_aligned) {
 #ifdef C1_DISABLE      // A/B build (tools/build_variant.sh): the generic small-Cout kernel everywhere
   return false;
 #endif
@@ -735,7 +795,7 @@ bool c1_eligible(const K3Args& a, int dtype, int y_dtype) {
   // per SAMPLE (which kernel a pair runs on must not depend on how a batch is split over ranks)
   if ((int64_t)a.D * a.H * a.W < C1_MIN_VOXELS || (int64_t)a.Cin * a.D * a.H * a.W >= (1ll << 31)) return false;
   // (a destination-channel offset moves the base by D*H*W elements, a multiple of 4 with W)
-  return a.x_bstride % 4 == 0 && a.y_bstride % 4 == 0 && aligned4(a.x, dtype) && aligned4(a.y, y_dtype);
+  return a.x_bstride % 4 == 0 && a.y_bstride % 4 == 0 && x_aligned && y_aligned;
 }
 
 template <class T, class TO>

@@ -621,7 +621,7 @@ int64_t x3_packed_words(int Cout, int Cin);
 // both sections of the packed weights (fp32-MFMA section of `total_k3` floats, then the bf16x3 fragments) in ONE launch
 // (`all` = false: the fp32-MFMA section only)
 // conv3d_c1.hip: the single-output-channel form (the head's last_3_3d at full resolution)
-bool c1_eligible(const K3Args& a, int dtype, int y_dtype);
+bool c1_eligible(const K3Args& a, bool x_aligned, bool y_aligned);
 int c1_launch(const K3Args& k, int dtype, int y_dtype, hipStream_t st);
 int pack_both(const float* w, float* packed, int64_t total_k3, int Cout, int Cin, int transpose, int planar, bool all, hipStream_t s);
 // Which kernel a 3x3x3 call runs on, in order of precedence: the depth-1 split-operand kernel (conv2d_x3.hip), the deep-level box kernel

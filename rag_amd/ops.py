@@ -1381,6 +1381,22 @@ def trilinear3d_route(in_size: Sequence[int], size: Sequence[int], channels: int
     return TRILINEAR_ROUTES[r]
 
 
+def conv3d_k3_small_route(cin: int, cout: int, B: int, D: int, H: int, W: int, dtype: torch.dtype = torch.float32,
+                          out_dtype: Optional[torch.dtype] = None, has_res: bool = False, x_bstride: Optional[int] = None,
+                          y_bstride: Optional[int] = None, x_align_ok: bool = True, y_align_ok: bool = True) -> int:
+    """The kernel conv3d_k3_small runs this call on (ragmi_conv3d_k3_small_route): 0 = conv3d_c1_kernel, 1 + cfg = the VALU form of
+    conv3d_k3_kernel on tile configuration cfg (0: x-tile 32, 1: 16, 2: 8).  out_dtype defaults to dtype; the batch strides (in
+    elements) default to those of contiguous [B, Cin, D, H, W] / [B, Cout, D, H, W] tensors; x_align_ok / y_align_ok: the data
+    pointers are aligned to four elements.  Needs no GPU."""
+    xb = cin * D * H * W if x_bstride is None else x_bstride
+    yb = cout * D * H * W if y_bstride is None else y_bstride
+    r = load_library().ragmi_conv3d_k3_small_route(int(cin), int(cout), int(B), int(D), int(H), int(W), _DT[dtype], _DT[out_dtype or dtype],
+                                                   int(bool(has_res)), int(xb), int(yb), int(bool(x_align_ok)), int(bool(y_align_ok)))
+    if r < 0:
+        check(r, "conv3d_k3_small_route")
+    return r
+
+
 def sgd_clip_step(param: torch.Tensor, grad: torch.Tensor, buf: torch.Tensor, lr: float, momentum: float, weight_decay: float,
                   max_norm: float, first_step: bool, workspace: Optional[torch.Tensor] = None,
                   norm_out: Optional[torch.Tensor] = None) -> torch.Tensor:
