@@ -815,6 +815,47 @@ int ragmi_selfsup_loss_fwd(const void* left, const void* right, const void* disp
 int ragmi_selfsup_loss_bwd(const void* unit_grad, const void* gout, void* grad, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Occlusion-aware self-supervised step: the two-view batch, the left-right consistency check and the weighted loss.
+ *
+ * ragmi_lr_stack_fwd: out_left = [left ; mirror_x(right)], out_right = [right ; mirror_x(left)], both [2B,C,H,W] fp32 from left,
+ * right [B,C,H,W] fp32 (mirror_x(v)[x] = v[W-1-x]).  Sample i < B is the ordinary pair, sample i + B the pair seen from the right
+ * camera.  One launch that only moves data (a kernel, not a memcpy node); the outputs are the caller's and must not alias the
+ * inputs.
+ *
+ * ragmi_lr_check_fwd: disp [B,H,W] fp32, disparities in their own view; the partner map of image b is
+ * partner[(b + partner_shift) mod B], read mirrored along x when mirrored != 0 (element x is p[W-1-x]; never materialised).
+ * Per pixel, d = disp[b,y,x], xr = x - d:
+ *   in view     iff d is finite and 0 <= xr <= W-1;
+ *   d'          = (1-f) p[x0] + f p[x1], x0 = floor(xr), x1 = min(x0+1, W-1), f = xr - x0, on the (mirrored) partner row;
+ *   e           = |d - d'|;
+ *   consistent  iff in view, e finite and e <= max(abs_tol, rel_tol |d|).
+ * weight[b,y,x] = 1 if consistent, else occluded_weight (in [0, 1]); err[b,y,x] = e if in view and finite, else +inf (err may be
+ * NULL); valid[b] = float(double(consistent pixels of image b) / double(H W)).  A non-finite d or tap stays in its own pixel and is
+ * never used as an index.  For the stacked batch: disp = partner = the [2B,H,W] output, partner_shift = B, mirrored = 1.
+ * workspace: ragmi_lr_check_workspace_elems(B,H,W) 4-byte elements, scratch.  Refused before any launch: a null pointer (but err),
+ * B < 1, H < 1, W < 2, partner_shift outside [0, B), a tolerance that is negative or not finite, an occluded_weight outside [0, 1]
+ * or not finite.  Two launches; integer counts per workgroup slot folded in a fixed order: no atomics, no memset, bitwise
+ * reproducible, no host synchronisation. */
+int ragmi_lr_stack_fwd(const void* left, const void* right, void* out_left, void* out_right, int B, int C, int H, int W, void* stream);
+int64_t ragmi_lr_check_workspace_elems(int B, int H, int W);
+int ragmi_lr_check_fwd(const void* disp, const void* partner, int B, int H, int W, int partner_shift, int mirrored, float abs_tol,
+                       float rel_tol, float occluded_weight, void* workspace, void* weight, void* err, void* valid, void* stream);
+
+/* ragmi_selfsup_loss_fwd with a per-pixel weight w = weight [B,H,W] fp32 (finite and non-negative: the caller's contract; constant,
+ * no gradient flows to it) on the photometric terms; wb = avg_pool2d(w, 3), the mean of w over each 3x3 SSIM block:
+ *   out[2] = L1   = sum_{b,c,y,x} w |left - left_est| / (C sum w);
+ *   out[1] = SSIM = sum_{blocks,c} wb term / (C sum wb), term the clamped (1 - S)/2 of ragmi_selfsup_loss_fwd;
+ *   out[3] = smoothness, unchanged and unweighted;   out[0] = 0.85 out[1] + 0.15 out[2] + 0.1 out[3].
+ * A term whose weights sum to 0 is 0, and so is its gradient.  Other arguments and restrictions as ragmi_selfsup_loss_fwd;
+ * workspace: ragmi_selfsup_loss_weighted_workspace_elems(B,H,W) floats, 8-byte aligned.  Four launches (a fixed-order pre-pass
+ * leaves sum w and sum wb as two doubles on the device, the main kernel reads them): no atomics, no memset or memcpy, no host
+ * synchronisation, bitwise reproducible.  _bwd: grad[i] = gout[0] * unit_grad[i] (ragmi_selfsup_loss_bwd's launch). */
+int64_t ragmi_selfsup_loss_weighted_workspace_elems(int B, int H, int W);
+int ragmi_selfsup_loss_weighted_fwd(const void* left, const void* right, const void* disp, const void* weight, int B, int C, int H,
+                                    int W, int dtype, void* workspace, void* out, void* unit_grad, void* stream);
+int ragmi_selfsup_loss_weighted_bwd(const void* unit_grad, const void* gout, void* grad, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Depth head of the monocular-depth network (rag_depth/src/models/rag_model.py:51-64, 357-416) as ONE launch:
  *   u   = bilinear(y, (H, W), align_corners=True)                      (upsample_6)
  *   m   = conv3x3(u, w3[1, Cin, 3, 3]), zero padding 1, no bias         (last_3_3d: bn=False, relu=False)

@@ -158,6 +158,14 @@ SIGNATURES = {
     "ragmi_selfsup_loss_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
     "ragmi_selfsup_loss_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ragmi_lr_stack_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ragmi_lr_check_workspace_elems": (c_int64, [c_int, c_int, c_int]),
+    "ragmi_lr_check_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
+    "ragmi_selfsup_loss_weighted_workspace_elems": (c_int64, [c_int, c_int, c_int]),
+    "ragmi_selfsup_loss_weighted_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                c_void_p, c_void_p, c_void_p]),
+    "ragmi_selfsup_loss_weighted_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ragmi_depth_head_supported": (c_int, [c_int] * 7),
     "ragmi_depth_head_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_int, c_void_p]),

@@ -161,3 +161,9 @@ class MultiTaskStereo(nn.Module):
         if not 0 <= t < len(self.archis):
             raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
         return self.net.forward_mode(left, right, t, self.archis[t], radius=radius, out=out, stats=stats, mode=mode)
+
+    def forward_lr(self, left, right, t: int, **check_kw):
+        """Both views' disparities and their left-right checks (Network.forward_lr); inference only."""
+        if not 0 <= t < len(self.archis):
+            raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
+        return self.net.forward_lr(left, right, t, self.archis[t], **check_kw)

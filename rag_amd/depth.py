@@ -373,6 +373,11 @@ class Network(_StereoNetwork):
     search_forward_mode = forward_mode
     forward_train_stats = forward_stats
 
+    def forward_lr(self, *args, **kwargs):
+        """The left-right check needs a second view: the depth network sees the left image only."""
+        raise NotImplementedError("rag_amd.depth.Network: forward_lr belongs to the stereo network (a left-right consistency check); "
+                                  "the depth network has no second view")
+
     def search_forward_train(self, left, t, selected_ops):         # rag_model.py:716-740 under autograd (approaches/rag.py:405)
         """The training forward of a sampled path: `search_forward` on the composition of `forward_train`, -> depth [B, 3h, 3w] with
         an autograd graph.  The module modes are the caller's (`search_mode()`: the trunk's BatchNorms on running statistics, the

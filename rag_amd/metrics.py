@@ -538,37 +538,49 @@ def sparsification(disp: torch.Tensor, unc: torch.Tensor, gt: torch.Tensor, maxd
 SELFSUP_NAMES = ("loss", "ssim", "l1", "smooth")
 
 
-def _selfsup_raw(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor, want_grad: bool):
-    """(out[4], unit gradient or None) of ragmi_selfsup_loss_fwd; nothing leaves the device."""
-    for t in (disp_est, left, right):
-        if not t.is_cuda:
+def _selfsup_raw(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor, want_grad: bool, weight: Optional[torch.Tensor] = None):
+    """(out[4], unit gradient or None) of ragmi_selfsup_loss_fwd, or of ragmi_selfsup_loss_weighted_fwd with `weight` [B, H, W];
+    nothing leaves the device."""
+    for t in (disp_est, left, right, weight):
+        if t is not None and not t.is_cuda:
             raise RuntimeError("rag_amd ops run on the MI355X only (got a CPU tensor); there is no CPU fallback")
     if disp_est.dim() != 3 or left.dim() != 4 or right.shape != left.shape or left.shape[0] != disp_est.shape[0] \
             or tuple(left.shape[2:]) != tuple(disp_est.shape[1:]):
         raise ValueError("re_and_sm_loss: disp_est must be [B, H, W] and left, right [B, C, H, W]")
-    dtypes = {disp_est.dtype, left.dtype, right.dtype}
+    if weight is not None and weight.shape != disp_est.shape:
+        raise ValueError("re_and_sm_loss: weight must be [B, H, W] like disp_est")
+    dtypes = {disp_est.dtype, left.dtype, right.dtype} | ({weight.dtype} if weight is not None else set())
     dt = ops._DT.get(disp_est.dtype, -1) if len(dtypes) == 1 else -1     # the library refuses what it was not built for
     B, C, H, W = left.shape
     d, lt, rt = disp_est.contiguous(), left.contiguous(), right.contiguous()
     lib = load_library()
-    ws = torch.empty((max(1, lib.ragmi_selfsup_loss_workspace_elems(B, H, W)),), device=d.device, dtype=torch.float32)
     out = torch.empty((4,), device=d.device, dtype=torch.float32)
     ug = torch.empty((B, H, W), device=d.device, dtype=torch.float32) if want_grad else None
-    check(lib.ragmi_selfsup_loss_fwd(lt.data_ptr(), rt.data_ptr(), d.data_ptr(), B, C, H, W, dt, ws.data_ptr(), out.data_ptr(),
-                                     ug.data_ptr() if ug is not None else None, ops._stream()), "selfsup_loss_fwd")
+    if weight is None:
+        ws = torch.empty((max(1, lib.ragmi_selfsup_loss_workspace_elems(B, H, W)),), device=d.device, dtype=torch.float32)
+        check(lib.ragmi_selfsup_loss_fwd(lt.data_ptr(), rt.data_ptr(), d.data_ptr(), B, C, H, W, dt, ws.data_ptr(), out.data_ptr(),
+                                         ug.data_ptr() if ug is not None else None, ops._stream()), "selfsup_loss_fwd")
+        return out, ug
+    w = weight.contiguous()
+    ws = torch.empty((max(1, lib.ragmi_selfsup_loss_weighted_workspace_elems(B, H, W)),), device=d.device, dtype=torch.float32)
+    check(lib.ragmi_selfsup_loss_weighted_fwd(lt.data_ptr(), rt.data_ptr(), d.data_ptr(), w.data_ptr(), B, C, H, W, dt, ws.data_ptr(),
+                                              out.data_ptr(), ug.data_ptr() if ug is not None else None, ops._stream()),
+          "selfsup_loss_weighted_fwd")
     return out, ug
 
 
 class SelfSupervisedLossFn(torch.autograd.Function):
     """re_and_sm_loss (src_self/models/loss.py:112-141) of disp_est [B,H,W] against the images it was computed from: one fused
     forward that also writes d loss / d disp_est at unit scale, and a backward that scales it by the incoming gradient.  Images get
-    no gradient (the reference's step never asks for one)."""
+    no gradient (the reference's step never asks for one), and neither does `weight` (a constant of the weighted form)."""
 
     @staticmethod
-    def forward(ctx, disp_est, left, right):
-        out, ug = _selfsup_raw(disp_est.detach(), left.detach(), right.detach(), ctx.needs_input_grad[0])
+    def forward(ctx, disp_est, left, right, weight=None):
+        out, ug = _selfsup_raw(disp_est.detach(), left.detach(), right.detach(), ctx.needs_input_grad[0],
+                               weight.detach() if weight is not None else None)
         if ug is not None:
             ctx.save_for_backward(ug)
+        ctx.weighted = weight is not None
         return out[0] * 1.0          # a kernel, not a memcpy node (as MaskedSmoothL1Fn)
 
     @staticmethod
@@ -576,26 +588,33 @@ class SelfSupervisedLossFn(torch.autograd.Function):
         (ug,) = ctx.saved_tensors
         gout = gout.reshape(1).contiguous().float()
         g = torch.empty_like(ug)
-        check(load_library().ragmi_selfsup_loss_bwd(ug.data_ptr(), gout.data_ptr(), g.data_ptr(), ug.numel(), ops._stream()),
-              "selfsup_loss_bwd")
-        return g, None, None
+        lib = load_library()
+        bwd = lib.ragmi_selfsup_loss_weighted_bwd if ctx.weighted else lib.ragmi_selfsup_loss_bwd
+        check(bwd(ug.data_ptr(), gout.data_ptr(), g.data_ptr(), ug.numel(), ops._stream()), "selfsup_loss_bwd")
+        return g, None, None, None
 
 
-def re_and_sm_loss(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+def re_and_sm_loss(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The self-supervised training loss of src_self (models/loss.py:112-141) under the reference's name: 0.85 SSIM + 0.15 L1
-    of `right` warped to `left` by disp_est, + 0.1 edge-aware smoothness; differentiable in disp_est (HIP, fp32)."""
-    return SelfSupervisedLossFn.apply(disp_est, left, right)
+    of `right` warped to `left` by disp_est, + 0.1 edge-aware smoothness; differentiable in disp_est (HIP, fp32).  `weight` [B,H,W]
+    (finite, non-negative, e.g. LRCheck.weight; a constant: no gradient flows to it): L1 = sum w |left - left_est| / (C sum w),
+    SSIM = sum wb term / (C sum wb) with wb = avg_pool2d(w, 3), smoothness unweighted; a term whose weights sum to 0 is 0.  None
+    takes the unweighted kernel."""
+    if weight is None:
+        return SelfSupervisedLossFn.apply(disp_est, left, right)
+    return SelfSupervisedLossFn.apply(disp_est, left, right, weight)
 
 
-def self_supervised_terms(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+def self_supervised_terms(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The 4-float device vector (loss, SSIM_mean, L1_mean, smoothness) of re_and_sm_loss for logging: no gradient, no sync."""
     with torch.no_grad():
-        return _selfsup_raw(disp_est.detach(), left.detach(), right.detach(), False)[0]
+        return _selfsup_raw(disp_est.detach(), left.detach(), right.detach(), False, weight.detach() if weight is not None else None)[0]
 
 
-def re_and_sm_loss_torch(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor):
+def re_and_sm_loss_torch(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor, weight: Optional[torch.Tensor] = None):
     """Plain-torch restatement of re_and_sm_loss in the dtype and on the device of its inputs (host twin of the CPU step, and the
-    fp64 / ATen yardstick of the tests and tools/bench_selfsup.py).  Returns (loss, (ssim_mean, l1_mean, smooth_mean))."""
+    fp64 / ATen yardstick of the tests and tools/bench_selfsup.py).  Returns (loss, (ssim_mean, l1_mean, smooth_mean)).  `weight`
+    [B,H,W]: the weighted form of re_and_sm_loss (a constant; a term whose weights sum to 0 is 0)."""
     import torch.nn.functional as F
     B, C, H, W = left.shape
     dt, dev = disp_est.dtype, disp_est.device
@@ -607,16 +626,149 @@ def re_and_sm_loss_torch(disp_est: torch.Tensor, left: torch.Tensor, right: torc
         cover = F.grid_sample(torch.ones_like(right[:, :1]), grid.detach(), mode="bilinear", padding_mode="zeros", align_corners=False)
         keep = (cover >= 0.9999).to(dt)
     est = sample * keep
-    l1 = (left - est).abs().mean()
     mu_x, mu_y = F.avg_pool2d(left, 3), F.avg_pool2d(est, 3)                    # stride 3: non-overlapping blocks
     var_x = F.avg_pool2d(left * left, 3) - mu_x * mu_x
     var_y = F.avg_pool2d(est * est, 3) - mu_y * mu_y
     cov = F.avg_pool2d(left * est, 3) - mu_x * mu_y
     c1, c2 = 1e-4, 9e-4
     s = (2 * mu_x * mu_y + c1) * (2 * cov + c2) / ((mu_x * mu_x + mu_y * mu_y + c1) * (var_x + var_y + c2))
-    ssim = torch.clamp((1 - s) / 2, 0, 1).mean()
+    term = torch.clamp((1 - s) / 2, 0, 1)
+    if weight is None:
+        l1 = (left - est).abs().mean()
+        ssim = term.mean()
+    else:
+        w = weight.detach().to(dt)[:, None]
+        wb = F.avg_pool2d(w, 3)
+
+        def wmean(num, den):                                                    # 0 where the weights sum to 0 (never 0 / 0)
+            return torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(num))
+        l1 = wmean((w * (left - est).abs()).sum(), C * w.sum())
+        ssim = wmean((wb * term).sum(), C * wb.sum())
     wx = torch.exp(-(left[..., :, :-1] - left[..., :, 1:]).mean(1).abs())
     wy = torch.exp(-(left[..., :-1, :] - left[..., 1:, :]).mean(1).abs())
     smooth = (((disp_est[..., :, :-1] - disp_est[..., :, 1:]).abs() * wx).sum()
               + ((disp_est[..., :-1, :] - disp_est[..., 1:, :]).abs() * wy).sum()) / (B * H * W)
     return 0.85 * ssim + 0.15 * l1 + 0.1 * smooth, (ssim, l1, smooth)
+
+
+# --------------------------------------------------------------------------- left-right consistency (occlusion-aware adaptation step)
+class LRCheck:
+    """Result of `lr_consistency`: `.weight` [B,H,W] is 1 where the pixel's disparity agrees with the other view's and
+    `occluded_weight` elsewhere (the `weight=` of re_and_sm_loss), `.error` [B,H,W] the disagreement |d - d'| in px (+inf where the
+    pixel's match lies outside the other image or a value is not finite; None with want_error=False), `.valid` [B] the consistent
+    share of each image, `.mask` the boolean `weight == 1`.  Everything stays on the device."""
+
+    def __init__(self, weight: torch.Tensor, error: Optional[torch.Tensor], valid: torch.Tensor):
+        self.weight, self.error, self.valid = weight, error, valid
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self.weight == 1
+
+
+def _lr_args(disp: torch.Tensor, partner: torch.Tensor, abs_tol, rel_tol, occluded_weight, partner_shift) -> None:
+    import math
+    if disp.dim() != 3 or partner.shape != disp.shape:
+        raise ValueError("lr_consistency: disp_left and disp_right must both be [B, H, W]")
+    if disp.shape[0] < 1 or disp.shape[1] < 1 or disp.shape[2] < 2:
+        raise ValueError("lr_consistency: needs B, H >= 1 and W >= 2")
+    for name, v in (("abs_tol", abs_tol), ("rel_tol", rel_tol)):
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError(f"lr_consistency: {name} must be finite and non-negative, got {v!r}")
+    if not (math.isfinite(occluded_weight) and 0 <= occluded_weight <= 1):
+        raise ValueError(f"lr_consistency: occluded_weight must lie in [0, 1], got {occluded_weight!r}")
+    if int(partner_shift) != partner_shift or not 0 <= int(partner_shift) < disp.shape[0]:
+        raise ValueError(f"lr_consistency: partner_shift must be an integer in [0, {disp.shape[0]}), got {partner_shift!r}")
+
+
+def lr_consistency_torch(disp_left: torch.Tensor, disp_right: torch.Tensor, abs_tol: float = 1.0, rel_tol: float = 0.0,
+                         occluded_weight: float = 0.0, mirrored: bool = False, partner_shift: int = 0, want_error: bool = True) -> LRCheck:
+    """Plain-torch twin of `lr_consistency` in the dtype and on the device of its inputs (the CPU path, and the float64 / ATen
+    yardstick of the tests and tools/bench_lr_check.py).  The three parameters are rounded to float32 first, as the C ABI takes them."""
+    _lr_args(disp_left, disp_right, abs_tol, rel_tol, occluded_weight, partner_shift)
+    with torch.no_grad():
+        d = disp_left.detach()
+        dt, dev = d.dtype, d.device
+        B, H, W = d.shape
+        a_tol, r_tol, occ = (torch.tensor(float(v), dtype=torch.float32, device=dev).to(dt) for v in (abs_tol, rel_tol, occluded_weight))
+        p = disp_right.detach().to(dt)
+        if int(partner_shift):
+            p = torch.roll(p, -int(partner_shift), 0)                          # p[b] = partner[(b + shift) mod B]
+        if mirrored:
+            p = p.flip(-1)
+        xr = torch.arange(W, device=dev, dtype=dt).view(1, 1, W) - d
+        in_view = torch.isfinite(d) & (xr >= 0) & (xr <= W - 1)
+        xs = torch.where(in_view, xr, torch.zeros_like(xr))                    # a value out of view is never an index
+        x0f = torch.floor(xs)
+        x0 = x0f.long()
+        x1 = torch.clamp(x0 + 1, max=W - 1)
+        f = xs - x0f
+        e = (d - ((1 - f) * torch.gather(p, 2, x0) + f * torch.gather(p, 2, x1))).abs()
+        seen = in_view & torch.isfinite(e)
+        inf = torch.full_like(e, float("inf"))
+        ok = seen & (torch.where(seen, e, inf) <= torch.maximum(a_tol, r_tol * d.abs()))
+        weight = torch.where(ok, torch.ones_like(e), occ.expand_as(e))
+        valid = (ok.sum((1, 2)).double() / float(H * W)).float()
+        return LRCheck(weight, torch.where(seen, e, inf) if want_error else None, valid)
+
+
+def lr_consistency(disp_left: torch.Tensor, disp_right: torch.Tensor, abs_tol: float = 1.0, rel_tol: float = 0.0,
+                   occluded_weight: float = 0.0, mirrored: bool = False, partner_shift: int = 0, want_error: bool = True) -> LRCheck:
+    """Left-right consistency check of disp_left [B,H,W] against the other view's disparity disp_right [B,H,W] (both positive for a
+    point in front of the cameras, each in its view's coordinates such that pixel x of the first matches x - d of the second).  Per
+    pixel d = disp_left[b,y,x] is looked up at x - d in the partner map (linear along the row) and the pixel is consistent when its
+    match lies inside the image and |d - d'| <= max(abs_tol, rel_tol |d|); occluded pixels and mismatches are not.  -> LRCheck
+    (.weight: 1 / occluded_weight, .error, .valid, .mask).  `partner_shift`: image b is checked against
+    disp_right[(b + partner_shift) mod B]; `mirrored`: the partner row is read mirrored along x.  With both, the [2B,H,W] output D
+    of a forward on the `lr_stack` batch checks itself: lr_consistency(D, D, mirrored=True, partner_shift=B).  One fused HIP pass
+    (two launches, no synchronisation, bitwise reproducible); no gradient; on CPU tensors the plain-torch twin runs."""
+    refuse_autograd("lr_consistency", disp_left, disp_right)
+    if not disp_left.is_cuda:
+        return lr_consistency_torch(disp_left, disp_right, abs_tol, rel_tol, occluded_weight, mirrored, partner_shift, want_error)
+    ops._need_gpu(disp_left, disp_right)
+    _lr_args(disp_left, disp_right, abs_tol, rel_tol, occluded_weight, partner_shift)
+    if disp_left.dtype != torch.float32 or disp_right.dtype != torch.float32:
+        raise RuntimeError(f"lr_consistency: float32 only (got {disp_left.dtype}, {disp_right.dtype})")
+    with torch.no_grad():
+        d, p = disp_left.detach().contiguous(), disp_right.detach().contiguous()
+        B, H, W = d.shape
+        lib = load_library()
+        ws = torch.empty((max(1, lib.ragmi_lr_check_workspace_elems(B, H, W)),), device=d.device, dtype=torch.int32)
+        weight = torch.empty_like(d)
+        err = torch.empty_like(d) if want_error else None
+        valid = torch.empty((B,), device=d.device, dtype=torch.float32)
+        check(lib.ragmi_lr_check_fwd(d.data_ptr(), p.data_ptr(), B, H, W, int(partner_shift), int(bool(mirrored)), float(abs_tol),
+                                     float(rel_tol), float(occluded_weight), ws.data_ptr(), weight.data_ptr(),
+                                     err.data_ptr() if err is not None else None, valid.data_ptr(), ops._stream()), "lr_check_fwd")
+        return LRCheck(weight, err, valid)
+
+
+def lr_stack(left: torch.Tensor, right: torch.Tensor, out=None):
+    """The two-view batch of the left-right check: (left2, right2) = ([left ; mirror_x(right)], [right ; mirror_x(left)]), both
+    [2B,C,H,W].  Sample i is the ordinary pair, sample i + B the pair seen from the right camera; mirrored along x it is again a
+    left / right pair, so one forward of the 2B batch gives both views' disparities (the right view's mirrored).  One HIP launch
+    (fp32; a kernel, so a captured step holds no memcpy node); torch.cat / flip on CPU tensors.  `out`: a pair of [2B,C,H,W]
+    buffers to write into.  No gradient."""
+    if left.dim() != 4 or right.shape != left.shape:
+        raise ValueError("lr_stack: left and right must both be [B, C, H, W]")
+    B, C, H, W = left.shape
+    if out is not None and (len(out) != 2 or any(tuple(o.shape) != (2 * B, C, H, W) or o.dtype != left.dtype or o.device != left.device
+                                                 or not o.is_contiguous() for o in out)):
+        raise ValueError("lr_stack: out must be a pair of contiguous [2B, C, H, W] tensors of left's dtype on its device")
+    with torch.no_grad():
+        lt, rt = left.detach(), right.detach()
+        if not lt.is_cuda:
+            l2, r2 = torch.cat((lt, rt.flip(-1))), torch.cat((rt, lt.flip(-1)))
+            if out is None:
+                return l2, r2
+            out[0].copy_(l2)
+            out[1].copy_(r2)
+            return out[0], out[1]
+        ops._need_gpu(lt, rt)
+        if lt.dtype != torch.float32 or rt.dtype != torch.float32:
+            raise RuntimeError(f"lr_stack: float32 only (got {lt.dtype}, {rt.dtype})")
+        lt, rt = lt.contiguous(), rt.contiguous()
+        l2, r2 = out if out is not None else (torch.empty((2 * B, C, H, W), device=lt.device, dtype=lt.dtype) for _ in range(2))
+        check(load_library().ragmi_lr_stack_fwd(lt.data_ptr(), rt.data_ptr(), l2.data_ptr(), r2.data_ptr(), B, C, H, W, ops._stream()),
+              "lr_stack_fwd")
+        return l2, r2

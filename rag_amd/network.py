@@ -201,6 +201,28 @@ class Network(MatchingNet):
             cost = self.search_matching(None, selected_ops, t, features=(lf, rf))
             return self.disp.forward_mode(cost, radius, out, stats, mode)
 
+    def forward_lr(self, left, right, t, task_arch=None, path=None, **check_kw):
+        """Both views' disparities and their left-right consistency from ONE forward of the stacked 2B batch
+        (rag_amd.metrics.lr_stack: sample i + B is the pair seen from the right camera, mirrored along x) and one check launch
+        (lr_consistency(D, D, mirrored=True, partner_shift=B, **check_kw); check_kw: abs_tol, rel_tol, occluded_weight, want_error).
+        -> (disp_left, disp_right, check_left, check_right): each disparity [B,H,W] and each LRCheck in its own camera's coordinates
+        (the right one mirrored back), disparities positive in both; inference only."""
+        from .metrics import LRCheck, lr_consistency, lr_stack
+        refuse_autograd("Network.forward_lr", left, right)
+        for k in check_kw:
+            if k not in ("abs_tol", "rel_tol", "occluded_weight", "want_error"):
+                raise TypeError(f"Network.forward_lr: unexpected keyword {k!r} (mirrored and partner_shift are set by the stacked form)")
+        with torch.no_grad():
+            B = left.shape[0]
+            left2, right2 = lr_stack(left, right)
+            disp = self.forward(left2, right2, t, task_arch, path)
+            chk = lr_consistency(disp, disp, mirrored=True, partner_shift=B, **check_kw)
+
+            def back(v):                                    # the right camera's half, mirrored back into its own coordinates
+                return v[B:].flip(-1) if v is not None else None
+            return (disp[:B], back(disp), LRCheck(chk.weight[:B], chk.error[:B] if chk.error is not None else None, chk.valid[:B]),
+                    LRCheck(back(chk.weight), back(chk.error), chk.valid[B:]))
+
     # ------------------------------------------------------------------ the unit search's step (Appr.search_epoch, rag.py:344-406)
     def search_mode(self):
         """The module modes of search_epoch (rag.py:345-368): train() on the root, then eval() on every unit of the stems,

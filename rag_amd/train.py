@@ -84,14 +84,15 @@ def masked_smooth_l1(disp: torch.Tensor, gt: torch.Tensor, maxdisp: int, meter=N
     return (per * mask).sum() / mask.sum()
 
 
-def self_supervised_loss(disp: torch.Tensor, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+def self_supervised_loss(disp: torch.Tensor, left: torch.Tensor, right: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
     """re_and_sm_loss(disp, left, right) of src_self/models/loss.py:112-141, the loss of the supervise=False step
-    (src_self/approaches/rag.py:270-278): the fused HIP loss of rag_amd.metrics on the GPU."""
+    (src_self/approaches/rag.py:270-278): the fused HIP loss of rag_amd.metrics on the GPU.  `weight` [B,H,W]: its weighted form
+    (rag_amd.metrics.re_and_sm_loss), the loss of the occlusion=True step."""
     if disp.is_cuda:
         from .metrics import re_and_sm_loss as fused
-        return fused(disp, left, right)
+        return fused(disp, left, right, weight)
     from .metrics import re_and_sm_loss_torch           # host-side twin (CPU tests of the step logic)
-    return re_and_sm_loss_torch(disp, left, right)[0]
+    return re_and_sm_loss_torch(disp, left, right, weight)[0]
 
 
 def uncertainty_loss(disp: torch.Tensor, stats: torch.Tensor, gt: torch.Tensor, maxdisp: int, var_floor: float = 1.0 / 12.0) -> torch.Tensor:
@@ -118,6 +119,33 @@ def _check_uncertainty(uncertainty: bool, net, supervise: bool, sampled_ops, sel
     if meter is not None:
         raise ValueError("uncertainty=True: an EpochMeter is fed by the masked smooth-L1 launch, which this step does not run: meter is "
                          "refused")
+
+
+def _check_occlusion(occlusion: bool, net, supervise: bool, features: bool, sampled_ops, selected_ops, uncertainty: bool, meter,
+                     lr_tol, occluded_weight) -> None:
+    """Argument checks of occlusion=True, before any launch."""
+    if not occlusion:
+        return
+    if supervise:
+        raise ValueError("occlusion=True weights the self-supervised loss: supervise=True is refused")
+    if features:
+        raise ValueError("occlusion=True needs the images (it stacks and mirrors them): features=True is refused")
+    if sampled_ops is not None:
+        raise ValueError("occlusion=True is built for the grown stereo Network: sampled_ops (the cell search's supernet) is refused")
+    if selected_ops is not None:
+        raise ValueError("occlusion=True is built for the grown stereo Network: selected_ops (the unit search) is refused")
+    if uncertainty:
+        raise ValueError("occlusion=True and uncertainty=True are two different losses: their combination is refused")
+    if meter is not None:
+        raise ValueError("occlusion=True: an EpochMeter is fed by the masked smooth-L1 launch, which this step does not run: meter is "
+                         "refused")
+    if _is_depth(net) or _supernet_kind(net) is not None:
+        raise ValueError("occlusion=True needs a second view: a depth network or a supernet is refused")
+    import math
+    if len(lr_tol) != 2 or not all(math.isfinite(v) and v >= 0 for v in lr_tol):
+        raise ValueError(f"occlusion=True: lr_tol must be (abs_tol, rel_tol), finite and non-negative, got {lr_tol!r}")
+    if not (math.isfinite(occluded_weight) and 0 <= occluded_weight <= 1):
+        raise ValueError(f"occlusion=True: occluded_weight must lie in [0, 1], got {occluded_weight!r}")
 
 
 def _is_depth(net) -> bool:
@@ -197,7 +225,8 @@ TRAIN_PRECISION = "fp32"     # the reference's training step is fp32 (rag.py:204
 def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None, features: bool = False,
                      precision: Optional[str] = None, supervise: bool = True, sampled_ops: Optional[Sequence] = None,
                      selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None, uncertainty: bool = False,
-                     var_floor: float = 1.0 / 12.0):
+                     var_floor: float = 1.0 / 12.0, occlusion: bool = False, lr_tol: Sequence[float] = (1.0, 0.0),
+                     occluded_weight: float = 0.0):
     """forward -> masked smooth-L1 -> zero the bucket -> backward (rag.py:208-214).  A depth network (rag_amd.depth.Network):
     Network.forward_train(left) -> silog_loss(depth, gt) with gt the ground-truth depth in metres (0 = invalid) as in
     rag_depth/src/approaches/rag.py:232-242; `right` may be None.  `supervise=False`: the self-supervised loss
@@ -217,7 +246,15 @@ def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None
     `uncertainty=True` (the grown stereo Network, or a MatchingNet with features=True; supervised): forward_train_stats in place of
     forward and rag_amd.metrics.uncertainty_loss(disp, stats, gt, net.maxdisp, var_floor) in place of the masked smooth-L1, so the
     variance the head reports is trained; supervise=False, sampled_ops, selected_ops, a depth network and a meter are refused.
+    `occlusion=True` (with supervise=False, the grown stereo Network on images): the occlusion-aware form of the self-supervised
+    step.  The batch is stacked with its mirrored right-camera view (rag_amd.metrics.lr_stack), ONE forward runs on the 2B pairs
+    (train-mode BatchNorm statistics are those of the 2B batch), the detached disparities are checked against each other
+    (lr_consistency(D, D, *lr_tol, occluded_weight, mirrored=True, partner_shift=B)) and the loss is
+    re_and_sm_loss(D, left2, right2, weight=check.weight) over all 2B pairs: both views train, and a pixel that is occluded in the
+    other view or whose disparity disagrees with it counts `occluded_weight` in the photometric terms (the smoothness term fills
+    it).  supervise=True, features=True, sampled_ops, selected_ops, uncertainty, a meter and a depth network are refused.
     Returns the (detached) loss."""
+    _check_occlusion(occlusion, net, supervise, features, sampled_ops, selected_ops, uncertainty, meter, lr_tol, occluded_weight)
     _check_uncertainty(uncertainty, net, supervise, sampled_ops, selected_ops, meter)
     sel = _check_selected(net, selected_ops, t, gt, sampled_ops, task_arch, features, supervise)
     kind = _check_sampled(net, sampled_ops, gt, task_arch, features, supervise)
@@ -243,6 +280,14 @@ def forward_backward(net, bucket: GradBucket, left, right, gt, *, task_arch=None
             res = net.forward_train_stats(left, right, task_arch) if features else \
                 net.forward_train_stats(left, right, 0, task_arch if task_arch is not None else net.arch_init)
             loss = uncertainty_loss(res.disp, res.tensor, gt, net.maxdisp, var_floor)
+        elif occlusion:
+            from .metrics import lr_consistency, lr_stack
+            left2, right2 = lr_stack(left, right)
+            disp = net(left2, right2, 0, task_arch if task_arch is not None else net.arch_init)
+            seen = disp.detach()
+            chk = lr_consistency(seen, seen, float(lr_tol[0]), float(lr_tol[1]), float(occluded_weight), mirrored=True,
+                                 partner_shift=left.shape[0], want_error=False)
+            loss = self_supervised_loss(disp, left2, right2, chk.weight)
         else:
             disp = net(left, right, task_arch) if features else net(left, right, 0, task_arch if task_arch is not None else net.arch_init)
             loss = masked_smooth_l1(disp, gt, net.maxdisp, meter) if supervise else self_supervised_loss(disp, left, right)
@@ -378,14 +423,16 @@ def search_eval_step(net, left, right, gt, t, selected_ops, meter=None):
 def train_step(net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                features: bool = False, precision: Optional[str] = None, supervise: bool = True,
                sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None,
-               uncertainty: bool = False, var_floor: float = 1.0 / 12.0):
+               uncertainty: bool = False, var_floor: float = 1.0 / 12.0, occlusion: bool = False, lr_tol: Sequence[float] = (1.0, 0.0),
+               occluded_weight: float = 0.0):
     """One optimisation step as in Appr.train_epoch (rag.py:204-216); `precision`, `supervise`, `sampled_ops`, `selected_ops` / `t`,
-    `meter` and `uncertainty` / `var_floor` as in forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops`
+    `meter`, `uncertainty` / `var_floor` and `occlusion` / `lr_tol` / `occluded_weight` as in forward_backward (defaults: fp32, supervised, a grown network).  With `sampled_ops`
     the optimizer updates net.active_parameters(*sampled_ops) only (exchange_and_update), with `selected_ops` (one batch of
     Appr.search_epoch, rag.py:371-396) net.active_parameters(t, selected_ops).  Returns the (detached) loss."""
     loss = forward_backward(net, bucket, left, right, gt, task_arch=task_arch, features=features, precision=precision,
                             supervise=supervise, sampled_ops=sampled_ops, selected_ops=selected_ops, t=t, meter=meter,
-                            uncertainty=uncertainty, var_floor=var_floor)
+                            uncertainty=uncertainty, var_floor=var_floor, occlusion=occlusion, lr_tol=lr_tol,
+                            occluded_weight=occluded_weight)
     active = _active_of(net, sampled_ops, selected_ops, t)
     exchange_and_update(optimizer, bucket, clip=clip, dist=dist, active=active)
     return loss
@@ -477,12 +524,18 @@ class GraphedTrainStep(_GraphedStep):
     `meter.last` stays the static vector the replays rewrite.
 
     `uncertainty=True, var_floor=`: the uncertainty-aware step of forward_backward; the statistics launch, the loss and both adjoints are
-    kernels, so the census holds as for the plain step."""
+    kernels, so the census holds as for the plain step.
+
+    `occlusion=True, lr_tol=, occluded_weight=` (with supervise=False): the occlusion-aware step of forward_backward.  The static
+    inputs stay [B, ...]; the stacked 2B batch, the check and its weight are buffers inside the captured graph, and the stack, the
+    check and the weighted loss are kernels, so the census holds."""
 
     def __init__(self, net, optimizer, bucket: GradBucket, left, right, gt, *, task_arch=None, clip: float = 5.0, dist=None,
                  features: bool = False, warmup: int = 2, precision: Optional[str] = None, supervise: bool = True,
                  sampled_ops: Optional[Sequence] = None, selected_ops: Optional[Sequence] = None, t: Optional[int] = None, meter=None,
-                 uncertainty: bool = False, var_floor: float = 1.0 / 12.0):
+                 uncertainty: bool = False, var_floor: float = 1.0 / 12.0, occlusion: bool = False,
+                 lr_tol: Sequence[float] = (1.0, 0.0), occluded_weight: float = 0.0):
+        _check_occlusion(occlusion, net, supervise, features, sampled_ops, selected_ops, uncertainty, meter, lr_tol, occluded_weight)
         _check_uncertainty(uncertainty, net, supervise, sampled_ops, selected_ops, meter)
         sel = _check_selected(net, selected_ops, t, gt, sampled_ops, task_arch, features, supervise)
         if _check_sampled(net, sampled_ops, gt, task_arch, features, supervise) is None and sel is None:
@@ -495,7 +548,8 @@ class GraphedTrainStep(_GraphedStep):
         self.gt = gt.clone() if gt is not None else None
         self.precision = precision or TRAIN_PRECISION
         kw = dict(task_arch=task_arch, features=features, precision=self.precision, supervise=supervise, sampled_ops=sampled_ops,
-                  selected_ops=sel, t=t, meter=meter, uncertainty=uncertainty, var_floor=var_floor)
+                  selected_ops=sel, t=t, meter=meter, uncertainty=uncertainty, var_floor=var_floor, occlusion=occlusion,
+                  lr_tol=tuple(lr_tol), occluded_weight=occluded_weight)
         self._capture(lambda: forward_backward(net, bucket, self.left, self.right, self.gt, **kw), warmup)
 
     def __call__(self, left=None, right=None, gt=None):
