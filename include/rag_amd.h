@@ -856,6 +856,35 @@ int ragmi_selfsup_loss_weighted_fwd(const void* left, const void* right, const v
 int ragmi_selfsup_loss_weighted_bwd(const void* unit_grad, const void* gout, void* grad, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Dense disparity: fill what a keep map (the left-right check's weight, or any mask) rejects, by background interpolation.
+ *
+ * ragmi_disp_fill_fwd: disp [B,H,W] fp32; keep [B,H,W], uint8 with non-zero = keep (keep_is_u8 != 0) or fp32 with == 1.0f = keep
+ * (keep_is_u8 == 0; ragmi_lr_check_fwd's weight as it is).  A pixel is RELIABLE iff it is kept and its disparity is finite; a
+ * value that is not reliable is never read as a value.
+ *   Row pass, for a row with at least one reliable pixel; L / R = the nearest reliable pixel left / right of an unreliable x:
+ *     both exist: out = (v[R] < v[L]) ? v[R] : v[L] (the farther surface; a tie or a signed zero takes the left value), code 1;
+ *     one exists: out = that value, code 2;        a reliable pixel: out = its value, bit for bit, code 0.
+ *   Column pass, for a row without a reliable pixel; U / D = the nearest rows above / below that have one, r = the row pass's result:
+ *     both exist: out = (r[D,x] < r[U,x]) ? r[D,x] : r[U,x], code 3;     one exists: that one, code 4;
+ *     neither (the image has no reliable pixel): out = fill_value, code 5.
+ * out [B,H,W] fp32 (every value a copy of a reliable input or fill_value: finite), code [B,H,W] uint8, counts [B,6] int32 (pixels
+ * per code), density [B] fp32 = float(double(counts[b,0]) / double(H W)).  workspace: ragmi_disp_fill_workspace_elems(B,H,W) 4-byte
+ * elements (a flag per row, six counts per workgroup), scratch.  out must not alias disp or keep.  Any H, W >= 1.
+ * Three launches (row pass, column pass, count finalize); integer counts per workgroup slot folded in a fixed order: no atomics, no
+ * memset or memcpy, no host synchronisation, bitwise reproducible; every output and every workspace element read is written first.
+ *
+ * ragmi_disp_median_fwd: out[b,y,x] = the median (the (m*m+1)/2-th smallest) of the m x m values in[b, clamp(y+j,0,H-1),
+ * clamp(x+i,0,W-1)], |i|, |j| <= m/2, m = 3 or 5; in, out [B,H,W] fp32, in != out; the result is a copy of one of them (finite
+ * inputs: the caller's contract, ragmi_disp_fill_fwd's out satisfies it).  One launch.
+ *
+ * Refused before any launch, without touching a pointer: a null pointer, a size < 1, a fill_value that is not finite, m other than
+ * 3 or 5, in == out, a workspace that is not 4-byte aligned, sizes whose grid or per-image pixel count would pass 2^31 - 1. */
+int64_t ragmi_disp_fill_workspace_elems(int B, int H, int W);
+int ragmi_disp_fill_fwd(const void* disp, const void* keep, int keep_is_u8, int B, int H, int W, float fill_value, void* workspace,
+                        void* out, void* code, void* counts, void* density, void* stream);
+int ragmi_disp_median_fwd(const void* in, void* out, int B, int H, int W, int m, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Depth head of the monocular-depth network (rag_depth/src/models/rag_model.py:51-64, 357-416) as ONE launch:
  *   u   = bilinear(y, (H, W), align_corners=True)                      (upsample_6)
  *   m   = conv3x3(u, w3[1, Cin, 3, 3]), zero padding 1, no bias         (last_3_3d: bn=False, relu=False)

@@ -166,6 +166,10 @@ SIGNATURES = {
     "ragmi_selfsup_loss_weighted_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                                 c_void_p, c_void_p, c_void_p]),
     "ragmi_selfsup_loss_weighted_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ragmi_disp_fill_workspace_elems": (c_int64, [c_int, c_int, c_int]),
+    "ragmi_disp_fill_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    "ragmi_disp_median_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ragmi_depth_head_supported": (c_int, [c_int] * 7),
     "ragmi_depth_head_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_int, c_void_p]),

@@ -378,6 +378,11 @@ class Network(_StereoNetwork):
         raise NotImplementedError("rag_amd.depth.Network: forward_lr belongs to the stereo network (a left-right consistency check); "
                                   "the depth network has no second view")
 
+    def forward_dense(self, *args, **kwargs):
+        """The dense fill repairs what the left-right check rejects: the depth network has no such check."""
+        raise NotImplementedError("rag_amd.depth.Network: forward_dense belongs to the stereo network (it fills what the left-right "
+                                  "check rejects); the depth network has no second view")
+
     def search_forward_train(self, left, t, selected_ops):         # rag_model.py:716-740 under autograd (approaches/rag.py:405)
         """The training forward of a sampled path: `search_forward` on the composition of `forward_train`, -> depth [B, 3h, 3w] with
         an autograd graph.  The module modes are the caller's (`search_mode()`: the trunk's BatchNorms on running statistics, the

@@ -772,3 +772,142 @@ def lr_stack(left: torch.Tensor, right: torch.Tensor, out=None):
         check(load_library().ragmi_lr_stack_fwd(lt.data_ptr(), rt.data_ptr(), l2.data_ptr(), r2.data_ptr(), B, C, H, W, ops._stream()),
               "lr_stack_fwd")
         return l2, r2
+
+
+# --------------------------------------------------------------------------- dense disparity: fill what the keep map rejects
+FILL_CODES = ("kept", "row_min", "row_one_side", "column_min", "column_one_side", "fill_value")
+
+
+class FilledDisp:
+    """Result of `fill_disparity`: `.disp` [B,H,W] the dense map (with median=0 a kept pixel keeps its bits), `.code` [B,H,W] uint8
+    where each value came from (0 kept, 1 the smaller of the row's two neighbours, 2 its only neighbour, 3 / 4 the same along the
+    column for a row without a reliable pixel, 5 fill_value: FILL_CODES), `.counts` [B,6] int32 the pixels per code, `.density` [B]
+    the share of code 0, `.filled` the boolean `code != 0`.  Codes and counts describe the fill, not the median.  Everything stays
+    on the device."""
+
+    def __init__(self, disp: torch.Tensor, code: torch.Tensor, counts: torch.Tensor, density: torch.Tensor):
+        self.disp, self.code, self.counts, self.density = disp, code, counts, density
+
+    @property
+    def filled(self) -> torch.Tensor:
+        return self.code != 0
+
+
+def _fill_args(disp: torch.Tensor, keep, median, fill_value) -> torch.Tensor:
+    """The checks shared by the launch and its twin -> the keep tensor (an LRCheck gives its weight)."""
+    import math
+    if isinstance(keep, LRCheck):
+        keep = keep.weight
+    if not isinstance(disp, torch.Tensor) or not isinstance(keep, torch.Tensor):
+        raise TypeError("fill_disparity: disp must be a tensor and keep an LRCheck or a tensor")
+    if disp.dim() != 3 or keep.shape != disp.shape or min(disp.shape) < 1:
+        raise ValueError("fill_disparity: disp and keep must both be [B, H, W] with B, H, W >= 1")
+    if not disp.dtype.is_floating_point:
+        raise TypeError(f"fill_disparity: disp must be a floating-point map, got {disp.dtype}")
+    if keep.dtype not in (torch.bool, torch.uint8) and not keep.dtype.is_floating_point:
+        raise TypeError(f"fill_disparity: keep must be bool, uint8 (non-zero keeps) or a floating-point weight (== 1 keeps), got {keep.dtype}")
+    if keep.device != disp.device:
+        raise RuntimeError(f"fill_disparity: disp is on {disp.device} and keep on {keep.device} (a CPU and a GPU tensor do not mix)")
+    if isinstance(median, bool) or median not in (0, 3, 5):
+        raise ValueError(f"fill_disparity: median must be 0, 3 or 5, got {median!r}")
+    if isinstance(fill_value, bool) or not isinstance(fill_value, (int, float)) or not math.isfinite(fill_value):
+        raise ValueError(f"fill_disparity: fill_value must be a finite number, got {fill_value!r}")
+    return keep
+
+
+def _farther(later: torch.Tensor, first: torch.Tensor) -> torch.Tensor:
+    return torch.where(later < first, later, first)                             # (later < first) ? later : first, never fmin
+
+
+def _nearest(ok: torch.Tensor, dim: int):
+    """Along `dim`: the index of the nearest True at or before each position (-1: none) and at or after it (size: none)."""
+    n = ok.shape[dim]
+    shape = [1] * ok.dim()
+    shape[dim] = n
+    idx = torch.arange(n, device=ok.device).view(shape).expand_as(ok)
+    before = torch.where(ok, idx, torch.full_like(idx, -1)).cummax(dim).values
+    after = torch.where(ok, idx, torch.full_like(idx, n)).flip(dim).cummin(dim).values.flip(dim)
+    return before, after
+
+
+def median_disparity_torch(disp: torch.Tensor, m: int) -> torch.Tensor:
+    """The m x m median (m = 3, 5) of a finite map [B,H,W] over replicate-padded windows: the (m*m+1)/2-th smallest."""
+    if m not in (3, 5):
+        raise ValueError(f"median_disparity_torch: m must be 3 or 5, got {m!r}")
+    B, H, W = disp.shape
+    r = m // 2
+    ys = torch.arange(-r, H + r, device=disp.device).clamp(0, H - 1)
+    xs = torch.arange(-r, W + r, device=disp.device).clamp(0, W - 1)
+    padded = disp[:, ys][:, :, xs]
+    win = padded.unfold(1, m, 1).unfold(2, m, 1).reshape(B, H, W, m * m)
+    return win.sort(-1).values[..., (m * m) // 2].contiguous()
+
+
+def fill_disparity_torch(disp: torch.Tensor, keep, median: int = 0, fill_value: float = 0.0) -> FilledDisp:
+    """Plain-torch twin of `fill_disparity` in the dtype and on the device of its inputs (the CPU path, and the ATen yardstick of the
+    tests and tools/bench_disp_fill.py): cummax / cummin give the nearest reliable neighbour on each side, gather fetches it."""
+    keep = _fill_args(disp, keep, median, fill_value)
+    with torch.no_grad():
+        d = disp.detach()
+        k = keep.detach()
+        B, H, W = d.shape
+        reliable = ((k == 1) if k.dtype.is_floating_point else (k != 0)) & torch.isfinite(d)
+        v = torch.where(reliable, d, torch.zeros_like(d))                      # a value that is not reliable is never read
+        li, ri = _nearest(reliable, 2)
+        has_l, has_r = li >= 0, ri < W
+        v_l, v_r = torch.gather(v, 2, li.clamp(min=0)), torch.gather(v, 2, ri.clamp(max=W - 1))
+        both = has_l & has_r
+        row = torch.where(both, _farther(v_r, v_l), torch.where(has_l, v_l, v_r))
+        code = torch.where(reliable, torch.zeros_like(li), torch.where(both, torch.ones_like(li), torch.full_like(li, 2)))
+        row_ok = reliable.any(2)                                                # [B,H]: rows the row pass completes
+        ui, di = _nearest(row_ok, 1)
+        has_u, has_d = (ui >= 0)[..., None], (di < H)[..., None]
+        r_u = torch.gather(row, 1, ui.clamp(min=0)[..., None].expand(B, H, W))
+        r_d = torch.gather(row, 1, di.clamp(max=H - 1)[..., None].expand(B, H, W))
+        fill = torch.full_like(d, float(fill_value))
+        col = torch.where(has_u & has_d, _farther(r_d, r_u), torch.where(has_u, r_u, torch.where(has_d, r_d, fill)))
+        col_code = torch.where(has_u & has_d, 3, torch.where(has_u | has_d, 4, 5)).expand(B, H, W)
+        out = torch.where(row_ok[..., None], row, col)
+        code = torch.where(row_ok[..., None], code, col_code).to(torch.uint8)
+        counts = torch.stack([(code == c).sum((1, 2)) for c in range(6)], 1).to(torch.int32)
+        density = (counts[:, 0].double() / float(H * W)).float()
+        if median:
+            out = median_disparity_torch(out, median)
+        return FilledDisp(out, code, counts, density)
+
+
+def fill_disparity(disp: torch.Tensor, keep, median: int = 0, fill_value: float = 0.0) -> FilledDisp:
+    """Dense disparity from disp [B,H,W] and a keep map: an `LRCheck` (its .weight), a bool / uint8 tensor (non-zero keeps) or an
+    fp32 weight (== 1 keeps), by background interpolation.  A pixel is reliable iff it is kept and finite; an unreliable one takes
+    the SMALLER of the nearest reliable disparities to its left and right on its row ((v[R] < v[L]) ? v[R] : v[L]: the farther
+    surface, which is what lies behind an occluder), or the only one; a row without a reliable pixel takes the same rule along the
+    columns from the nearest rows that have one; an image without one becomes `fill_value`.  `median` = 3 or 5 then takes the
+    m x m median of the filled map (clamped at the border).  Every output value is a copy of a reliable input (or fill_value), so
+    the result is exact.  -> FilledDisp (.disp, .code, .counts, .density, .filled).  Three HIP launches (row scan, column pass, count
+    finalize) and one for the median: no atomics, no synchronisation, bitwise reproducible; fp32; no gradient; on CPU tensors the
+    plain-torch twin runs."""
+    keep = _fill_args(disp, keep, median, fill_value)
+    refuse_autograd("fill_disparity", disp, keep if keep.dtype.is_floating_point else None)
+    if not disp.is_cuda:
+        return fill_disparity_torch(disp, keep, median, fill_value)
+    if disp.dtype != torch.float32 or (keep.dtype.is_floating_point and keep.dtype != torch.float32):
+        raise RuntimeError(f"fill_disparity: float32 only (got {disp.dtype}, keep {keep.dtype})")
+    with torch.no_grad():
+        d, k = disp.detach().contiguous(), keep.detach().contiguous()
+        is_u8 = k.dtype != torch.float32
+        if k.dtype == torch.bool:
+            k = k.view(torch.uint8)                                             # the same bytes: no launch
+        B, H, W = d.shape
+        lib = load_library()
+        ws = torch.empty((lib.ragmi_disp_fill_workspace_elems(B, H, W),), device=d.device, dtype=torch.int32)
+        out = torch.empty_like(d)
+        code = torch.empty((B, H, W), device=d.device, dtype=torch.uint8)
+        counts = torch.empty((B, 6), device=d.device, dtype=torch.int32)
+        density = torch.empty((B,), device=d.device, dtype=torch.float32)
+        check(lib.ragmi_disp_fill_fwd(d.data_ptr(), k.data_ptr(), int(is_u8), B, H, W, float(fill_value), ws.data_ptr(), out.data_ptr(),
+                                      code.data_ptr(), counts.data_ptr(), density.data_ptr(), ops._stream()), "disp_fill_fwd")
+        if median:
+            smooth = torch.empty_like(out)
+            check(lib.ragmi_disp_median_fwd(out.data_ptr(), smooth.data_ptr(), B, H, W, int(median), ops._stream()), "disp_median_fwd")
+            out = smooth
+        return FilledDisp(out, code, counts, density)
