@@ -885,6 +885,46 @@ int ragmi_disp_fill_fwd(const void* disp, const void* keep, int keep_is_u8, int 
 int ragmi_disp_median_fwd(const void* in, void* out, int B, int H, int W, int m, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Speckle filter: segment a disparity map into connected regions of similar disparity and reject the small ones (the step between
+ * the left-right check and ragmi_disp_fill_fwd; OpenCV's filterSpeckles).
+ *
+ * ragmi_speckle_fwd: disp [B,H,W] fp32; keep [B,H,W] by keep_kind: 0 = fp32 weight (== 1.0f keeps; ragmi_lr_check_fwd's weight as
+ * it is), 1 = uint8 (non-zero keeps), 2 = none (every pixel is kept; keep may then be NULL).  max_size: integer >= 0; max_diff:
+ * finite, >= 0.
+ *   A pixel is RELIABLE iff it is kept and its disparity is finite (ragmi_disp_fill_fwd's own rule); a value that is not reliable is
+ *   never read as a value.
+ *   Two 4-neighbours p, q are JOINED iff both are reliable and fabsf(d_p - d_q) <= max_diff, evaluated in fp32 as one IEEE
+ *   subtraction, one absolute value and one comparison, no other arithmetic; a difference that overflows to Inf does not join;
+ *   diagonal neighbours never join.
+ *   A SEGMENT is a connected component of that graph: similarity is per edge, so a ramp 5.0, 5.8, 6.6 with max_diff = 1 is one segment.
+ * Outputs:
+ *   label    [B,H,W] int32  the smallest y*W + x of the pixel's segment (a per-image index); -1 for an unreliable pixel
+ *   size     [B,H,W] int32  the segment's pixel count; 0 for an unreliable pixel
+ *   keep_out [B,H,W] uint8  1 iff reliable and size > max_size (a segment of at most max_size pixels is a speckle: OpenCV's rule;
+ *                           with max_size = 0 keep_out is "reliable" and the call is a pure labelling)
+ *   counts   [B,5]   int32  RAGMI_SPECKLE_COUNTS: reliable pixels, segments, removed pixels, removed segments, the largest segment's
+ *                           size (0 if there is none)
+ *   density  [B]     fp32   float(double(reliable - removed pixels) / double(H W))
+ * workspace: ragmi_speckle_workspace_elems(B,H,W) 4-byte elements (three per pixel: parent, tile-local count, total; five counts
+ * per workgroup of 1024 pixels; 0 for sizes that ragmi_speckle_fwd refuses), scratch.  The outputs must not alias the inputs.
+ * Any H, W >= 1.
+ * Five launches in a fixed sequence (tile labelling in LDS over RAGMI_SPECKLE_TILE_ROWS x RAGMI_SPECKLE_TILE_COLS tiles, lock-free
+ * union at the tile seams, flatten and total, apply, count finalize; the seam launch is absent where the image is a single tile): no
+ * loop over launches, no flag read by the host.  Integer atomics only (min, add: order-independent), no float atomics, no memset or
+ * memcpy, no host synchronisation, graph-capturable, bitwise reproducible; every output element and every workspace element that is
+ * read is written first by the call.
+ *
+ * Refused with status -1 before any launch, without touching a pointer: a null pointer (except keep with kind 2), a size < 1,
+ * max_size < 0, a max_diff that is negative or not finite, an unknown keep_kind, a workspace that is not 4-byte aligned, sizes whose
+ * grid or per-image pixel count would pass 2^31 - 1. */
+#define RAGMI_SPECKLE_TILE_ROWS 16
+#define RAGMI_SPECKLE_TILE_COLS 64
+#define RAGMI_SPECKLE_COUNTS 5
+int64_t ragmi_speckle_workspace_elems(int B, int H, int W);
+int ragmi_speckle_fwd(const void* disp, const void* keep, int keep_kind, int B, int H, int W, int max_size, float max_diff,
+                      void* workspace, void* label, void* size, void* keep_out, void* counts, void* density, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Depth head of the monocular-depth network (rag_depth/src/models/rag_model.py:51-64, 357-416) as ONE launch:
  *   u   = bilinear(y, (H, W), align_corners=True)                      (upsample_6)
  *   m   = conv3x3(u, w3[1, Cin, 3, 3]), zero padding 1, no bias         (last_3_3d: bn=False, relu=False)

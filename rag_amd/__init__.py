@@ -15,6 +15,7 @@ from . import train  # noqa: F401
 from .metrics import CalibrationMeter, DispMode, DispStats, EpochMeter, Sparsification, sparsification, uncertainty_loss  # noqa: F401
 from .metrics import LRCheck, lr_consistency, lr_consistency_torch, lr_stack, re_and_sm_loss, re_and_sm_loss_torch  # noqa: F401
 from .metrics import FilledDisp, fill_disparity, fill_disparity_torch  # noqa: F401
+from .metrics import Speckles, filter_speckles, filter_speckles_torch  # noqa: F401
 from .train import search_eval_step  # noqa: F401
 from .modules import (  # noqa: F401
     ALL_CONV_GENOTYPE, ALL_SKIP_GENOTYPE, Cell_3d, ConvBR_3d, Disp, DisparityRegression, Genotype,
@@ -39,6 +40,7 @@ __all__ = [
     "sparsification", "Sparsification", "CalibrationMeter",
     "LRCheck", "lr_consistency", "lr_consistency_torch", "lr_stack", "re_and_sm_loss", "re_and_sm_loss_torch",
     "FilledDisp", "fill_disparity", "fill_disparity_torch",
+    "Speckles", "filter_speckles", "filter_speckles_torch",
     "DepthEpochMeter", "depth_metrics", "silog_metrics_loss", "depth_search", "depth_search_step", "depth_search_eval_step",
     "DepthGraphedSearchStep",
     "Network", "Cell_2d", "ConvBR_2d", "DepthNetwork", "load_depth_checkpoint",

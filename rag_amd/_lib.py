@@ -170,6 +170,9 @@ SIGNATURES = {
     "ragmi_disp_fill_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
     "ragmi_disp_median_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ragmi_speckle_workspace_elems": (c_int64, [c_int, c_int, c_int]),
+    "ragmi_speckle_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
     "ragmi_depth_head_supported": (c_int, [c_int] * 7),
     "ragmi_depth_head_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_float, c_int, c_void_p]),

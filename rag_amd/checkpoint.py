@@ -168,8 +168,9 @@ class MultiTaskStereo(nn.Module):
             raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
         return self.net.forward_lr(left, right, t, self.archis[t], **check_kw)
 
-    def forward_dense(self, left, right, t: int, **kw):
-        """Both views' dense (filled) disparities and their left-right checks (Network.forward_dense); inference only."""
+    def forward_dense(self, left, right, t: int, speckle=None, **kw):
+        """Both views' dense (filled) disparities and their left-right checks (Network.forward_dense); `speckle` = (max_size,
+        max_diff) drops small disparity segments before the fill; inference only."""
         if not 0 <= t < len(self.archis):
             raise IndexError(f"MultiTaskStereo: task {t} not in [0, {len(self.archis)})")
-        return self.net.forward_dense(left, right, t, self.archis[t], **kw)
+        return self.net.forward_dense(left, right, t, self.archis[t], speckle=speckle, **kw)

@@ -782,11 +782,11 @@ class FilledDisp:
     """Result of `fill_disparity`: `.disp` [B,H,W] the dense map (with median=0 a kept pixel keeps its bits), `.code` [B,H,W] uint8
     where each value came from (0 kept, 1 the smaller of the row's two neighbours, 2 its only neighbour, 3 / 4 the same along the
     column for a row without a reliable pixel, 5 fill_value: FILL_CODES), `.counts` [B,6] int32 the pixels per code, `.density` [B]
-    the share of code 0, `.filled` the boolean `code != 0`.  Codes and counts describe the fill, not the median.  Everything stays
-    on the device."""
+    the share of code 0, `.filled` the boolean `code != 0`.  Codes and counts describe the fill, not the median.  `.speckles`: the
+    `Speckles` whose keep map was filled (Network.forward_dense(speckle=...)), else None.  Everything stays on the device."""
 
-    def __init__(self, disp: torch.Tensor, code: torch.Tensor, counts: torch.Tensor, density: torch.Tensor):
-        self.disp, self.code, self.counts, self.density = disp, code, counts, density
+    def __init__(self, disp: torch.Tensor, code: torch.Tensor, counts: torch.Tensor, density: torch.Tensor, speckles=None):
+        self.disp, self.code, self.counts, self.density, self.speckles = disp, code, counts, density, speckles
 
     @property
     def filled(self) -> torch.Tensor:
@@ -794,12 +794,14 @@ class FilledDisp:
 
 
 def _fill_args(disp: torch.Tensor, keep, median, fill_value) -> torch.Tensor:
-    """The checks shared by the launch and its twin -> the keep tensor (an LRCheck gives its weight)."""
+    """The checks shared by the launch and its twin -> the keep tensor (an LRCheck gives its weight, a Speckles its keep)."""
     import math
     if isinstance(keep, LRCheck):
         keep = keep.weight
+    elif isinstance(keep, Speckles):
+        keep = keep.keep
     if not isinstance(disp, torch.Tensor) or not isinstance(keep, torch.Tensor):
-        raise TypeError("fill_disparity: disp must be a tensor and keep an LRCheck or a tensor")
+        raise TypeError("fill_disparity: disp must be a tensor and keep an LRCheck, a Speckles or a tensor")
     if disp.dim() != 3 or keep.shape != disp.shape or min(disp.shape) < 1:
         raise ValueError("fill_disparity: disp and keep must both be [B, H, W] with B, H, W >= 1")
     if not disp.dtype.is_floating_point:
@@ -911,3 +913,135 @@ def fill_disparity(disp: torch.Tensor, keep, median: int = 0, fill_value: float 
             check(lib.ragmi_disp_median_fwd(out.data_ptr(), smooth.data_ptr(), B, H, W, int(median), ops._stream()), "disp_median_fwd")
             out = smooth
         return FilledDisp(out, code, counts, density)
+
+
+# --------------------------------------------------------------------------- speckle filter: drop small disparity segments before the fill
+SPECKLE_COUNTS = ("reliable", "segments", "removed_pixels", "removed_segments", "largest")
+SPECKLE_TILE = (16, 64)                         # RAGMI_SPECKLE_TILE_ROWS / _COLS of include/rag_amd.h: the tile of the first launch
+
+
+class Speckles:
+    """Result of `filter_speckles`: `.keep` [B,H,W] bool, True iff the pixel is reliable and its segment has more than max_size
+    pixels (a `keep` for fill_disparity), `.label` [B,H,W] int32 the smallest y*W + x of the pixel's segment (-1: unreliable), `.size`
+    [B,H,W] int32 the segment's pixel count (0: unreliable), `.counts` [B,5] int32 (SPECKLE_COUNTS: reliable pixels, segments, removed
+    pixels, removed segments, the largest segment's size), `.density` [B] the share of kept pixels, `.removed` the boolean
+    `(label >= 0) & ~keep`.  Everything stays on the device."""
+
+    def __init__(self, keep: torch.Tensor, label: torch.Tensor, size: torch.Tensor, counts: torch.Tensor, density: torch.Tensor):
+        self.keep, self.label, self.size, self.counts, self.density = keep, label, size, counts, density
+
+    @property
+    def removed(self) -> torch.Tensor:
+        return (self.label >= 0) & ~self.keep
+
+
+def _speckle_args(disp: torch.Tensor, keep, max_size, max_diff) -> Optional[torch.Tensor]:
+    """The checks shared by the launch and its twin -> the keep tensor (an LRCheck gives its weight) or None."""
+    import ctypes
+    import math
+    import numbers
+    if isinstance(keep, LRCheck):
+        keep = keep.weight
+    if not isinstance(disp, torch.Tensor) or not (keep is None or isinstance(keep, torch.Tensor)):
+        raise TypeError("filter_speckles: disp must be a tensor and keep an LRCheck, a tensor or None")
+    if disp.dim() != 3 or min(disp.shape) < 1 or (keep is not None and keep.shape != disp.shape):
+        raise ValueError("filter_speckles: disp and keep must both be [B, H, W] with B, H, W >= 1")
+    if not disp.dtype.is_floating_point:
+        raise TypeError(f"filter_speckles: disp must be a floating-point map, got {disp.dtype}")
+    if keep is not None:
+        if keep.dtype not in (torch.bool, torch.uint8) and not keep.dtype.is_floating_point:
+            raise TypeError("filter_speckles: keep must be bool, uint8 (non-zero keeps) or a floating-point weight (== 1 keeps), "
+                            f"got {keep.dtype}")
+        if keep.device != disp.device:
+            raise RuntimeError(f"filter_speckles: disp is on {disp.device} and keep on {keep.device} (a CPU and a GPU tensor do not mix)")
+    if isinstance(max_size, bool) or not isinstance(max_size, numbers.Integral) or not 0 <= max_size <= 0x7fffffff:
+        raise ValueError(f"filter_speckles: max_size must be an integer >= 0, got {max_size!r}")
+    if (isinstance(max_diff, bool) or not isinstance(max_diff, numbers.Real) or not math.isfinite(max_diff) or max_diff < 0
+            or not math.isfinite(ctypes.c_float(max_diff).value)):
+        raise ValueError(f"filter_speckles: max_diff must be a finite number >= 0 (in float32), got {max_diff!r}")
+    return keep
+
+
+def filter_speckles_torch(disp: torch.Tensor, keep=None, max_size: int = 100, max_diff: float = 1.0) -> Speckles:
+    """Plain-torch twin of `filter_speckles` in the dtype and on the device of its inputs (the CPU path, and the ATen yardstick of the
+    tests and tools/bench_speckle.py).  Every pixel holds the index of a pixel of its own segment that is not larger than its own; a
+    round takes the minimum over the joined neighbours' and then jumps to that pixel's own pointer, until a round changes nothing
+    (one host synchronisation per round); scatter_add counts the sizes.  max_diff is rounded to float32 first, as the C ABI takes it."""
+    keep = _speckle_args(disp, keep, max_size, max_diff)
+    with torch.no_grad():
+        d = disp.detach()
+        B, H, W = d.shape
+        n, dev = H * W, d.device
+        reliable = torch.isfinite(d)
+        if keep is not None:
+            k = keep.detach()
+            reliable = reliable & ((k == 1) if k.dtype.is_floating_point else (k != 0))
+        md = torch.tensor(float(max_diff), dtype=torch.float32, device=dev).to(d.dtype)
+        v = torch.where(reliable, d, torch.zeros_like(d))                      # a value that is not reliable is never read
+        right = reliable[..., :-1] & reliable[..., 1:] & ((v[..., :-1] - v[..., 1:]).abs() <= md)      # [B,H,W-1]: x joined to x + 1
+        down = reliable[:, :-1] & reliable[:, 1:] & ((v[:, :-1] - v[:, 1:]).abs() <= md)               # [B,H-1,W]: y joined to y + 1
+        idx = torch.arange(n, device=dev).view(1, H, W).expand(B, H, W)
+        none = torch.full((B, H, W), n, device=dev, dtype=idx.dtype)           # slot n: the unreliable pixels', it points at itself
+        lab = torch.where(reliable, idx, none)
+        while True:
+            new = lab.clone()
+            new[..., 1:] = torch.minimum(new[..., 1:], torch.where(right, lab[..., :-1], none[..., 1:]))
+            new[..., :-1] = torch.minimum(new[..., :-1], torch.where(right, lab[..., 1:], none[..., 1:]))
+            new[:, 1:] = torch.minimum(new[:, 1:], torch.where(down, lab[:, :-1], none[:, 1:]))
+            new[:, :-1] = torch.minimum(new[:, :-1], torch.where(down, lab[:, 1:], none[:, 1:]))
+            flat = torch.cat((new.reshape(B, n), none.reshape(B, n)[:, :1]), 1)
+            for _ in range(2):                                                  # pointer jumping
+                flat = flat.gather(1, flat)
+            new = flat[:, :n].reshape(B, H, W)
+            if torch.equal(new, lab):
+                break
+            lab = new
+        flat = lab.reshape(B, n)
+        total = torch.zeros((B, n + 1), device=dev, dtype=flat.dtype).scatter_add_(1, flat, torch.ones_like(flat))
+        size = torch.where(reliable, total.gather(1, flat).reshape(B, H, W), torch.zeros_like(lab))
+        kept = reliable & (size > int(max_size))
+        root = reliable & (lab == idx)
+        gone = reliable & ~kept
+        counts = torch.stack((reliable.sum((1, 2)), root.sum((1, 2)), gone.sum((1, 2)), (root & gone).sum((1, 2)),
+                              size.amax((1, 2))), 1).to(torch.int32)
+        density = ((counts[:, 0] - counts[:, 2]).double() / float(n)).float()
+        label = torch.where(reliable, lab, torch.full_like(lab, -1)).to(torch.int32)
+        return Speckles(kept, label, size.to(torch.int32), counts, density)
+
+
+def filter_speckles(disp: torch.Tensor, keep=None, max_size: int = 100, max_diff: float = 1.0) -> Speckles:
+    """Speckle filter of a disparity map disp [B,H,W] (OpenCV's filterSpeckles, on the device): `keep` is an `LRCheck` (its .weight), a
+    bool / uint8 tensor (non-zero keeps), an fp32 weight (== 1 keeps) or None (keep everything).  A pixel is reliable iff it is kept
+    and finite; two 4-neighbours are joined iff both are reliable and |d_p - d_q| <= max_diff (fp32: one subtraction, one comparison;
+    per edge, so a ramp of small steps is one segment; diagonals never join); a segment is a connected component and one of at most
+    `max_size` pixels is a speckle: its pixels leave the keep map.  max_size=0 removes nothing (a pure labelling).  The defaults
+    (100 px, 1 px) sit in the range OpenCV's SGBM documentation recommends (window 50-200, range 1-2): a convention, not something
+    tuned here.  -> Speckles (.keep, .label, .size, .counts, .density, .removed); pass it to fill_disparity as its keep.  Five HIP
+    launches (tile labelling in LDS, union at the tile seams, flatten, apply, count finalize): integer atomics only, no
+    synchronisation, bitwise reproducible, graph-capturable; fp32; no gradient; on CPU tensors the plain-torch twin runs."""
+    keep = _speckle_args(disp, keep, max_size, max_diff)
+    refuse_autograd("filter_speckles", disp, keep if keep is not None and keep.dtype.is_floating_point else None)
+    if not disp.is_cuda:
+        return filter_speckles_torch(disp, keep, max_size, max_diff)
+    if disp.dtype != torch.float32 or (keep is not None and keep.dtype.is_floating_point and keep.dtype != torch.float32):
+        raise RuntimeError(f"filter_speckles: float32 only (got {disp.dtype}, keep {keep.dtype if keep is not None else None})")
+    with torch.no_grad():
+        d = disp.detach().contiguous()
+        kind, k = 2, None
+        if keep is not None:
+            k = keep.detach().contiguous()
+            kind = 0 if k.dtype == torch.float32 else 1
+            if k.dtype == torch.bool:
+                k = k.view(torch.uint8)                                         # the same bytes: no launch
+        B, H, W = d.shape
+        lib = load_library()
+        ws = torch.empty((lib.ragmi_speckle_workspace_elems(B, H, W),), device=d.device, dtype=torch.int32)
+        label = torch.empty((B, H, W), device=d.device, dtype=torch.int32)
+        size = torch.empty_like(label)
+        kept = torch.empty((B, H, W), device=d.device, dtype=torch.uint8)
+        counts = torch.empty((B, len(SPECKLE_COUNTS)), device=d.device, dtype=torch.int32)
+        density = torch.empty((B,), device=d.device, dtype=torch.float32)
+        check(lib.ragmi_speckle_fwd(d.data_ptr(), k.data_ptr() if k is not None else None, kind, B, H, W, int(max_size), float(max_diff),
+                                    ws.data_ptr(), label.data_ptr(), size.data_ptr(), kept.data_ptr(), counts.data_ptr(),
+                                    density.data_ptr(), ops._stream()), "speckle_fwd")
+        return Speckles(kept.view(torch.bool), label, size, counts, density)                # 0 / 1 bytes: no launch

@@ -223,16 +223,28 @@ class Network(MatchingNet):
             return (disp[:B], back(disp), LRCheck(chk.weight[:B], chk.error[:B] if chk.error is not None else None, chk.valid[:B]),
                     LRCheck(back(chk.weight), back(chk.error), chk.valid[B:]))
 
-    def forward_dense(self, left, right, t, task_arch=None, path=None, median=0, fill_value=0.0, **check_kw):
+    def forward_dense(self, left, right, t, task_arch=None, path=None, median=0, fill_value=0.0, speckle=None, **check_kw):
         """forward_lr, then every pixel its check rejects filled on the device (rag_amd.metrics.fill_disparity: the smaller of the
         nearest consistent disparities on its row, rows without one along the columns, then an optional 3x3 / 5x5 median).
         -> (dense_left, dense_right, check_left, check_right): the checks are forward_lr's; each dense_* is the FilledDisp (.disp,
         .code, .counts, .density, .filled) of fill_disparity(that view's disparity, its check, median, fill_value), run per view in
-        that camera's own coordinates, so left and right mean the same in both.  check_kw as forward_lr; inference only."""
-        from .metrics import fill_disparity
+        that camera's own coordinates, so left and right mean the same in both.  `speckle` = (max_size, max_diff): each view's
+        disparity and check first go through rag_amd.metrics.filter_speckles, in the same coordinates; the fill takes its result in
+        place of the check and carries it as dense_*.speckles (None without).  check_kw as forward_lr; inference only."""
+        from .metrics import fill_disparity, filter_speckles
         refuse_autograd("Network.forward_dense", left, right)
+        if speckle is not None and (not isinstance(speckle, (tuple, list)) or len(speckle) != 2):
+            raise ValueError(f"Network.forward_dense: speckle must be None or (max_size, max_diff), got {speckle!r}")
         disp_l, disp_r, chk_l, chk_r = self.forward_lr(left, right, t, task_arch, path, **check_kw)
-        return (fill_disparity(disp_l, chk_l, median, fill_value), fill_disparity(disp_r, chk_r, median, fill_value), chk_l, chk_r)
+        if speckle is None:
+            return (fill_disparity(disp_l, chk_l, median, fill_value), fill_disparity(disp_r, chk_r, median, fill_value), chk_l, chk_r)
+
+        def dense(disp, chk):
+            spk = filter_speckles(disp, chk, speckle[0], speckle[1])
+            out = fill_disparity(disp, spk, median, fill_value)
+            out.speckles = spk
+            return out
+        return dense(disp_l, chk_l), dense(disp_r, chk_r), chk_l, chk_r
 
     # ------------------------------------------------------------------ the unit search's step (Appr.search_epoch, rag.py:344-406)
     def search_mode(self):
