@@ -637,9 +637,12 @@ class _Cell(nn.Module):
     def _one_launch_2d(self, s0, s1, size) -> bool:
         """A Cell_2d in which every new state is conv(s0) + conv(s1) (the all-conv genotype) can run as ONE launch — the two 1x1
         ConvBRs and their bilinear resamples in the staging of the dual 3x3 launch (ragmi_cell2d_fwd); s0 / s1 are never written.
-        The shape / dtype / precision half of that condition (the caller knows whether the cell is one dual launch)."""
+        The shape / dtype / precision half of that condition (the caller knows whether the cell is one dual launch).  Both INPUTS must
+        be depth-1 volumes too: the launch resamples in 2-D, and a Cell_3d that ends at depth 1 may read a deeper input (cell 5 of the
+        Matching Net on a d = 4 cost volume reads T[3] at depth 2)."""
         C, (D, H, W) = self.C_out, size
-        return (D == 1 and s0.shape[1] != C and s1.dtype == torch.float32 and s0.dtype == torch.float32
+        return (D == 1 and s0.shape[2] == 1 and s1.shape[2] == 1 and s0.shape[1] != C
+                and s1.dtype == torch.float32 and s0.dtype == torch.float32
                 and ops.get_conv_precision() == "f16x3" and ops.cell2d_supported(C, s0.shape[1], s1.shape[1], C * self._steps, H, W))
 
     def _run(self, prev_prev_input, prev_input, plan: Optional["_CellPlan"] = None, pre: Optional[torch.Tensor] = None,

@@ -684,6 +684,8 @@ def cell2d(s0: torch.Tensor, pre0, s1: torch.Tensor, pre1, C: int, packed_a: tor
         _need_gpu(w2d, sc, sh)
         if x.shape[0] != B or w2d.shape != (C, x.shape[1]) or not w2d.is_contiguous():
             raise ValueError("cell2d: input / 1x1 weight shapes do not match")
+        if x.dim() == 5 and x.shape[2] != 1:
+            raise ValueError("cell2d: a 5-D input must be a depth-1 volume (the launch resamples in 2-D)")
         ins.append(Cell2dIn(x.data_ptr(), _planes(x), x.shape[1], x.shape[-2], x.shape[-1], w2d.data_ptr(), p(sc), p(sh), int(bool(rl))))
     groups = list(out_group_ch) if out_group_ch is not None else [4 * g for g in range(cout // 4)]
     if len(groups) != cout // 4 or cout % 4 or any(g < 0 or g + 4 > out.shape[1] for g in groups):
