@@ -556,16 +556,11 @@ def _selfsup_raw(disp_est: torch.Tensor, left: torch.Tensor, right: torch.Tensor
     lib = load_library()
     out = torch.empty((4,), device=d.device, dtype=torch.float32)
     ug = torch.empty((B, H, W), device=d.device, dtype=torch.float32) if want_grad else None
-    if weight is None:
-        ws = torch.empty((max(1, lib.ragmi_selfsup_loss_workspace_elems(B, H, W)),), device=d.device, dtype=torch.float32)
-        check(lib.ragmi_selfsup_loss_fwd(lt.data_ptr(), rt.data_ptr(), d.data_ptr(), B, C, H, W, dt, ws.data_ptr(), out.data_ptr(),
-                                         ug.data_ptr() if ug is not None else None, ops._stream()), "selfsup_loss_fwd")
-        return out, ug
-    w = weight.contiguous()
-    ws = torch.empty((max(1, lib.ragmi_selfsup_loss_weighted_workspace_elems(B, H, W)),), device=d.device, dtype=torch.float32)
-    check(lib.ragmi_selfsup_loss_weighted_fwd(lt.data_ptr(), rt.data_ptr(), d.data_ptr(), w.data_ptr(), B, C, H, W, dt, ws.data_ptr(),
-                                              out.data_ptr(), ug.data_ptr() if ug is not None else None, ops._stream()),
-          "selfsup_loss_weighted_fwd")
+    name = "selfsup_loss" if weight is None else "selfsup_loss_weighted"
+    w = () if weight is None else (weight.contiguous(),)
+    ws = torch.empty((max(1, getattr(lib, f"ragmi_{name}_workspace_elems")(B, H, W)),), device=d.device, dtype=torch.float32)
+    check(getattr(lib, f"ragmi_{name}_fwd")(*(t.data_ptr() for t in (lt, rt, d) + w), B, C, H, W, dt, ws.data_ptr(), out.data_ptr(),
+                                            ug.data_ptr() if ug is not None else None, ops._stream()), f"{name}_fwd")
     return out, ug
 
 

@@ -1,4 +1,4 @@
-"""The weighted self-supervised loss (rag_amd/csrc/selfsup_loss_weighted.hip; rag_amd.metrics.re_and_sm_loss(..., weight=)) against
+"""The weighted self-supervised loss (rag_amd/csrc/selfsup_loss.hip; rag_amd.metrics.re_and_sm_loss(..., weight=)) against
 its plain-torch twin re_and_sm_loss_torch(..., weight=) in float64, on the remainder and workgroup-boundary rows of
 test_selfsup_sweep.py (tests/golden/g14_selfsup_edges.npz: inputs 1e-3 clear of each of the loss's kinks, which the weight, a constant
 factor per pixel, does not move).
@@ -264,6 +264,19 @@ def test_raw_call_is_deterministic_and_overwrites_nan(tag, kind):
         runs.append((out, ug))
     assert _same_bits(runs[0][0], runs[1][0]) and _same_bits(runs[0][1], runs[1][1])
     assert _same_bits(runs[0][0], terms) and _same_bits(runs[0][1], grad) and _same_bits(runs[0][0][:1], loss.reshape(1))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ("mask", "fraction"))
+@pytest.mark.parametrize("tag", TAGS)
+def test_terms_kernel_equals_gradient_kernel_bitwise(tag, kind):
+    """The terms-only instantiation (self_supervised_terms) returns the four floats of the raw call that also writes the gradient, bit
+    for bit: test_selfsup_sweep.py's property of the plain form, for the weighted one."""
+    from rag_amd import metrics
+    disp, left, right, w, _loss, grad, terms = _run(tag, kind)
+    out, ug = metrics._selfsup_raw(disp, left, right, True, w)
+    torch.cuda.synchronize()
+    assert _same_bits(out, terms) and _same_bits(ug, grad)
 
 
 @pytest.mark.gpu
